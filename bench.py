@@ -14,6 +14,10 @@ one proposal, one log-posterior evaluation and one accept/reject).  Inputs (spec
 walker positions) are resident in HBM before the timed region; the chain sample of every step is
 recorded device-to-device inside it.  Rank 0 prints ONE JSON line.
 
+`--dump-outputs DIR` writes, after the timed steps, what they computed (bench.py: dump_outputs).  The
+workload and the sampler seed are fixed, so two builds run with the same arguments can be compared
+array for array.
+
 Strong scaling: the 65 536 walkers are sharded over the N ranks (contiguous walker blocks), with
 one RCCL all-gather of the owned rows per half-step (vamp_amd/ensemble.py).
 """
@@ -311,6 +315,30 @@ def committed_pmc(P, K, W, D, world, dtype, workload="headline"):
 F_W_FLOPS, F_PX_FLOPS = 82.0, 46.0
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, outs, W, seed=12345):
+    """Write every per-walker array of ``outs`` as out_dir/<name>.npy (float64; accept counts are exact in it).
+    When all of them together exceed DUMP_BYTES_MAX, a fixed seeded sample of walker rows is written instead,
+    the same rows for every array, and their indices go to walker_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    outs = {k: np.asarray(v, dtype=np.float64) for k, v in outs.items()}      # each [W] or [W, D]
+    assert all(a.shape[0] == W for a in outs.values())
+    row_bytes = sum(8 * (a.size // W) for a in outs.values())
+    rows = None
+    if W * row_bytes > DUMP_BYTES_MAX:
+        n = DUMP_BYTES_MAX // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(W, n, replace=False))
+        outs = {k: a[rows] for k, a in outs.items()}
+        outs["walker_index"] = rows.astype(np.float64)
+    for k, a in outs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    total = sum(a.nbytes for a in outs.values())
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in outs), "bytes": total,
+            "walkers": W if rows is None else int(rows.size), "sampled": rows is not None}
+
+
 def self_launch(n_gpus):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a child process
     (`python -m torch.distributed.run`, one rank per GPU) and relay rank 0's line.  This parent never
@@ -365,7 +393,12 @@ def main():
     ap.add_argument("--exchange-parts", default="auto",
                     help="pieces per half-step of the overlapped exchange: a number, or 'auto' = time 1 and 2 during warm-up "
                          "and keep the faster (every rank takes the same decision from the max over ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (walker positions, log-posteriors, accept counts "
+                         "and the last recorded chain row) as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # the host driver of these boxes only supports dmabuf IPC: without this RCCL's intra-node handles fail
     # (hipIpcGetMemHandle: invalid argument).  Already exported on the boxes; kept for any other launcher.
@@ -534,6 +567,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
 
+    # what the timed steps computed, taken before the second run below moves the ensemble on
+    dumped = None
+    if args.dump_outputs:
+        X, lnp_all, nacc_all = ens.gather_state()            # collective when sharded: every rank calls it
+        outs = {"theta": X, "lnprob": lnp_all, "n_accept": nacc_all}
+        if chain is not None:
+            outs["chain_last"] = chain[args.steps - 1].view(W, D).cpu().numpy()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, outs, W)
+
     # a longer second run (clocks and caches settled; 20 steps are 0.15 s): same loop, the chain thinned
     # into the same buffer
     sustained = None
@@ -662,6 +705,8 @@ def main():
             "acceptance_fraction": acc_frac,
             "finite_lnprob_fraction": finite_frac,
         }
+        if dumped:
+            line["dump_outputs"] = dumped
         if sustained:
             sustained["value"] = W * sustained["steps"] / sustained["seconds"]
             sustained["ms_per_step"] = sustained["seconds"] / sustained["steps"] * 1e3

@@ -2,7 +2,7 @@
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library; the
  * product (vamp_amd) never does.  It restates the same reference arithmetic as
- * oracle/vamp_oracle.py (citations: /root/reference/vamp_1.0):
+ * oracle/vamp_oracle.py (citations: the reference's vamp_1.0 tree):
  *   Gaussian / Voigt tau-profiles   vpfits.py:43-54, 57-76
  *   flux = exp(-sum tau_k)          physics.py:98-105, vpfits.py:334-336
  *   chi^2 / Normal likelihood       vpfits.py:109-131, 39, 341

@@ -4,7 +4,7 @@ Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline``
 this module.  The product path (``vamp_amd``) never imports anything from ``oracle/``.
 
 It restates, in numpy + ``scipy.special.wofz``, the arithmetic of the reference hot path
-(``/root/reference/vamp_1.0``; citations are file:line in that tree):
+(the reference's ``vamp_1.0`` tree; citations are file:line in that tree):
 
   * Gaussian tau-profile                ``vpfits.py:43-54``
   * Voigt tau-profile                   ``vpfits.py:57-76`` (astropy ``Voigt1D`` in its wofz form,

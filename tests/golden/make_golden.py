@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Generate the committed golden fixtures under tests/golden/.
 
-Run in the BUILD container only (it reads /root/reference, which does not exist on the GPU box):
+    python tests/golden/make_golden.py [OUT_DIR] --reference PATH/TO/vamp_1.0    # every fixture
+    python tests/golden/make_golden.py [OUT_DIR]                                 # the oracle-computed ones
 
-    python tests/golden/make_golden.py
+The reference-computed fixtures and the data copies (``ref_statics``, ``simba_H1215.h5``,
+``simba_spectra``, ``q1422_vpm``, the integer columns of ``q1422_spectrum``) need the reference's
+``vamp_1.0`` tree.  Without it, the oracle-computed fixtures are regenerated from the committed
+data fixtures alone (tests/test_oracle.py does this and compares bit for bit).
 
 What is reference-computed and what is oracle-computed:
 
 * ``ref_statics.npz``  -- outputs of the REFERENCE's own numpy-only functions, imported from
-  /root/reference/vamp_1.0: ``physics.py`` (imports cleanly) and the statics of ``vpfits.VPfit``
+  the reference's vamp_1.0: ``physics.py`` (imports cleanly) and the statics of ``vpfits.VPfit``
   (``GaussFunction``, ``GaussianWidth``, ``Chisquared``, ``ReducedChisquared``).  ``vpfits.py``
   imports pymc and astropy at module level (absent here, ordinary ModuleNotFoundError); empty
   placeholder modules are inserted in ``sys.modules`` only so that the import statement succeeds --
@@ -34,7 +38,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = HERE      # where the fixtures are written (tests/test_oracle.py regenerates into a temp dir)
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REF = "/root/reference/vamp_1.0"
+REF = None      # the reference's vamp_1.0 tree (--reference); None = regenerate from the committed data
 
 from oracle import vamp_oracle as vo  # noqa: E402
 
@@ -319,13 +323,18 @@ def make_stretch(simba):
 def make_q1422():
     """vamp_1.0/data/q1422.cont (49 106 rows: wavelength, velocity, flux, noise), the spectrum of
     BASELINE.json config 3, stored as exact integers: the file prints 3 / 6 decimals, and
-    int/10^k reproduces the parsed double exactly (one correctly rounded division)."""
-    a = np.loadtxt(os.path.join(REF, "data", "q1422.cont"))
-    wl = np.rint(a[:, 0] * 1000).astype(np.int32)
-    fl = np.rint(a[:, 2] * 1e6).astype(np.int32)
-    no = np.rint(a[:, 3] * 1e6).astype(np.int32)
-    assert np.array_equal(wl / 1000.0, a[:, 0]) and np.array_equal(fl / 1e6, a[:, 2]) and np.array_equal(no / 1e6, a[:, 3])
-    px, wv = vo.compute_detection_regions_ref(a[:, 0], a[:, 2], a[:, 3])       # oracle, full-length kernels
+    int/10^k reproduces the parsed double exactly (one correctly rounded division).  Without the reference
+    the integer columns come from the committed fixture and the detection regions are recomputed."""
+    if REF is not None:
+        a = np.loadtxt(os.path.join(REF, "data", "q1422.cont"))
+        wl = np.rint(a[:, 0] * 1000).astype(np.int32)
+        fl = np.rint(a[:, 2] * 1e6).astype(np.int32)
+        no = np.rint(a[:, 3] * 1e6).astype(np.int32)
+        assert np.array_equal(wl / 1000.0, a[:, 0]) and np.array_equal(fl / 1e6, a[:, 2]) and np.array_equal(no / 1e6, a[:, 3])
+    else:
+        q = np.load(os.path.join(HERE, "q1422_spectrum.npz"), allow_pickle=False)
+        wl, fl, no = q["wavelength_milli"], q["flux_micro"], q["noise_micro"]
+    px, wv = vo.compute_detection_regions_ref(wl / 1000.0, fl / 1e6, no / 1e6)   # oracle, full-length kernels
     np.savez_compressed(os.path.join(OUT, "q1422_spectrum.npz"), wavelength_milli=wl, flux_micro=fl, noise_micro=no,
                         region_pixels=np.array(px, dtype=np.int32))
     print("q1422_spectrum.npz: %d pixels, %d regions" % (wl.size, len(px)))
@@ -348,21 +357,32 @@ def make_q1422_vpm():
     print("q1422_vpm.npz: %d lines" % a.shape[0])
 
 
-def make_all(out_dir=None):
-    """Write every fixture into ``out_dir`` (default: this directory)."""
-    global OUT
-    if not os.path.isdir(REF):
-        sys.exit("run in the build container: /root/reference is required")
+def make_all(out_dir=None, reference=None):
+    """Write the fixtures into ``out_dir`` (default: this directory): every one of them with the
+    reference's vamp_1.0 tree at ``reference``, the oracle-computed ones from the committed data without it."""
+    global OUT, REF
+    if reference is not None and not os.path.isdir(reference):
+        sys.exit("no reference tree at %s" % reference)
+    REF = reference
     if out_dir is not None:
         OUT = out_dir
-    make_ref_statics()
-    simba = make_simba()
+    if REF is not None:
+        make_ref_statics()
+        simba = make_simba()
+        make_q1422_vpm()
+    else:
+        g = np.load(os.path.join(HERE, "simba_spectra.npz"), allow_pickle=False)
+        simba = {k: g[k] for k in g.files}
     make_wofz_grid()
     make_lnprob_cases(simba)
     make_stretch(simba)
     make_q1422()
-    make_q1422_vpm()
 
 
 if __name__ == "__main__":
-    make_all(sys.argv[1] if len(sys.argv) > 1 else None)
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out_dir", nargs="?", default=None)
+    ap.add_argument("--reference", default=None, help="the reference's vamp_1.0 directory")
+    a = ap.parse_args()
+    make_all(a.out_dir, a.reference)

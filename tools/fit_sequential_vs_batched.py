@@ -3,7 +3,7 @@
 batched ladder, on the first N regions of the spectrum.   python tools/fit_sequential_vs_batched.py [N]   (GPU box)"""
 import os, sys, time, json
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa
 from vamp_amd.vpspectrum import VPspectrum
