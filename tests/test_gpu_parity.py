@@ -261,7 +261,8 @@ def test_packed_launch_classes_at_production_size(dtype):
     spectrum-like context -- four walkers per wavefront with 2-line and 8-line LDS layouts, draws from
     k_draws, and the 2-wavefront groups with Taylor tables -- run here at W = 32 768 on four q1422
     regions (1, 2, 3 and >= 4 lines).  fp64: lnprob of every walker and two full stretch steps of
-    every walker against the oracle.  fp32: chi^2 within the stated 1e-3."""
+    every walker against the oracle.  fp32: chi^2 within the stated 1e-3, and the two steps against the
+    oracle's stretch move evaluating its proposals with a second fp32 context (the same arithmetic)."""
     import vamp_amd
     from tools.bench_c3 import build_regions, start_walkers
     xs, fs, ns, ks = build_regions()
@@ -284,19 +285,29 @@ def test_packed_launch_classes_at_production_size(dtype):
                 assert np.max(np.abs(la[r] - want[r]) / np.maximum(1, np.abs(want[r]))) <= 1e-9, r
             else:
                 assert np.max(np.abs(la[r] - want[r]) / np.abs(want[r])) <= 1e-3, r
+        ev = None
         if dtype == "f32":
-            return
+            # vamp_lnprob runs W points of a region in the shape of a W-walker ensemble's W/2 movers: a half-step's W/2
+            # proposals, each twice, take the shape the device stepped them in
+            ev = vamp_amd.HipContext(device=0, dtype=vamp_amd.F32)
+            ev.set_regions(xs, fs, ns, ks, mode=vamp_amd.MODE_VOIGT4)
+            assert np.array_equal(ev.lnprob_all(th), la)
         ctx.sampler_init(th, seed=77, split_block=1024)
         res = ctx.run(2)
         for r, reg in enumerate(regs):
-            fn = lambda q, reg=reg: vo.log_prob_batch_fast(reg, q)
-            chain, lchain, nacc = vo.run_sampler_batch(fn, th[r], want[r], 2, seed=77, block=1024, region=r, walker_off=r * W)
+            if ev is None:
+                fn, lnp0 = (lambda q, reg=reg: vo.log_prob_batch_fast(reg, q)), want[r]
+            else:
+                fn, lnp0 = (lambda q, r=r: ev.lnprob(np.concatenate([q, q]), region=r)[:len(q)]), la[r]
+            chain, lchain, nacc = vo.run_sampler_batch(fn, th[r], lnp0, 2, seed=77, block=1024, region=r, walker_off=r * W)
             # an accept decision whose margin is at rounding level (|log u - diff| ~ 1e-13 of 65 536
             # decisions per region) may legitimately differ: allow a handful of walkers
             ok = np.all(np.abs(res["chain"][r] - chain) <= 1e-10 * np.abs(chain) + 1e-12, axis=(0, 2))
             assert (~ok).sum() <= 2, (r, int((~ok).sum()))
             assert np.abs(res["n_accept"][r] - nacc).sum() <= 2, r
             assert np.allclose(res["lnprob"][r][:, ok], lchain[:, ok], rtol=1e-9, atol=1e-9)
+        if ev is not None:
+            ev.close()
 
 
 def test_config2_shape_against_oracle(hip_ctx):
