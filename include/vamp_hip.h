@@ -162,7 +162,10 @@ int vamp_lnprob_all(vamp_ctx* ctx, int64_t W, const double* theta, double* lnpro
  * search, the others are returned unchanged.  A region whose search ends worse than its start
  * keeps the start.  lnprob_best[n_regions] and chi2_best (may be NULL) describe the returned
  * points; iterations (may be NULL) receives the simplex updates carried out per region (fmin
- * reports one more: it counts from 1, and like fmin the search stops at maxiter - 1 updates). */
+ * reports one more: it counts from 1, and like fmin the search stops at maxiter - 1 updates).  maxfun is
+ * checked at the top of an iteration only, as the PyMC-era fmin did: the iteration in which the count passes
+ * maxfun is finished (up to N + 1 evaluations more).  scipy's fmin since its _MaxFuncCallError change stops
+ * inside that iteration instead, so there the two can end on different points. */
 int vamp_map_all(vamp_ctx* ctx, const double* theta0, const uint8_t* active, int64_t maxiter,
                  int64_t maxfun, double xtol, double ftol, double* theta_best, double* lnprob_best,
                  double* chi2_best, int64_t* iterations);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer soak (not collected by pytest): the two device-resident loops of round 4 against their launch-per-step
 forms on RANDOM contexts -- every parameterisation, packing, ragged region mixes (1..8 lines, 9..330 px, now and then a
-region of 17..24 lines), even walker counts that fill their wavefronts or do not, thinning, continued runs:
+region of 9..16 or of 17..24 lines), even walker counts up to 256 (128 movers) that fill their wavefronts or do not,
+thinning, continued runs:
   * k_run_resident ("resident" = 2) vs one launch per half-step ("resident" = 0): chain, log-posterior chain,
     acceptance counts and final state bit for bit;
   * k_map_search ("map_device" = 1) vs the host-driven search (0): optimum bit for bit, same iteration counts.
@@ -26,8 +27,8 @@ def make(rng, variant, W, packing):
     for _ in range(n_regions):
         P = int(rng.choice([9, 14, 23, 36, 51, 64, 65, 97, 130, 200, 257, 330]))
         K = int(rng.integers(1, 9))
-        if packing in (0, 64) and rng.random() < 0.1:
-            K = int(rng.integers(17, 25))
+        if packing in (0, 64) and rng.random() < 0.2:
+            K = int(rng.integers(9, 17)) if rng.random() < 0.5 else int(rng.integers(17, 25))
         x = np.arange(P, dtype=np.float64) - (P - 1) / 2.0
         c = rng.uniform(x[0] * 0.8, x[-1] * 0.8, K)
         w = rng.uniform(1.0, 0.06 * P + 2.0, K)
@@ -64,7 +65,7 @@ bad = 0
 for c in range(n_ctx):
     rng = np.random.default_rng(31000 + c)
     variant, packing = c % 4, [0, 16, 64, 65, 0][(c // 4) % 5]
-    W = int(2 * rng.integers(4, 100))
+    W = int(2 * rng.integers(4, 129))
     divs = [b for b in range(2, W + 1, 2) if W % b == 0]
     block = int(rng.choice(divs))
     xs, fs, ns, Ks, ths, kw = make(rng, variant, W, packing)

@@ -18,6 +18,7 @@ from oracle import vamp_oracle as vo
 
 import test_gpu_parity as gp
 import test_gpu_vpfit as gv
+import test_gpu_map_classes as gm
 
 # VAMP_CPU_SO: another build of the same library (tests/test_sanitizers.py points it at the ASan/UBSan build)
 CPU_SO = os.environ.get("VAMP_CPU_SO") or os.path.join(ROOT, "oracle", "libvamp_cpu.so")
@@ -266,3 +267,28 @@ def test_host_plan_launch_classes_shards_and_grids(cpu_lib, cpu_ctx):
     # the resident loop's automatic policy: packed short-region classes, every mover in one round
     ok = cpu_lib.vampdbg_resident_class_ok
     assert ok(3, 16, 2, 8, 1) == 1 and ok(3, 17, 2, 8, 1) == 0 and ok(1, 16, 8, 1, 1) == 0 and ok(1, 16, 8, 1, 0) == 1 and ok(0, 16, 0, 4, 0) == 0
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("limits", list(gm.LIMITS))
+@pytest.mark.parametrize("case", gm.MAP_CASES)
+def test_map_search_follows_fmin_on_every_class_through_the_host_abi(cpu_lib, case, limits, dtype):
+    """tests/test_gpu_map_classes.py's MAP search against scipy's fmin (every launch class, D = 33 / 34 / 129, every
+    mode, both dtypes) through the host ABI; iterlim of the 129-dimensional region capped at 200 to keep it short"""
+    import vamp_amd
+    with vamp_amd.HipContext(dtype=vamp_amd.F64 if dtype == "f64" else vamp_amd.F32, lib=cpu_lib) as ctx:
+        gm.map_follows_fmin(ctx, case, limits, oracle_bar=dtype, iter_cap_d129=200)
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("case", gm.MAP_CASES)
+def test_point_alone_equals_point_in_a_batch_through_the_host_abi(cpu_lib, case, dtype):
+    import vamp_amd
+    with vamp_amd.HipContext(dtype=vamp_amd.F64 if dtype == "f64" else vamp_amd.F32, lib=cpu_lib) as ctx:
+        gm.point_alone_equals_point_in_a_batch(ctx, case)
+
+
+@pytest.mark.parametrize("case", ["gauss-sd", "voigt-sd", "nbz"])
+def test_map_search_maxfun_rule_through_the_host_abi(cpu_ctx, case):
+    """maxfun is checked at the top of an iteration (tests/test_gpu_map_classes.py::map_maxfun_rule), on the host"""
+    gm.map_maxfun_rule(cpu_ctx, case)

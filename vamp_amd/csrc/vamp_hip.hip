@@ -567,8 +567,22 @@ __device__ __forceinline__ double table_eval(const double* tab, double x) {
     return r;
 }
 
+// true when pred holds on some active lane of this lane's walker group (LPW lanes; the wavefront when LPW = 64).  The
+// branches of the tile evaluators below are voted per group, not per wavefront: every branch is accurate but not
+// bit-identical to the others, and a vote over the wavefront would make a walker's value depend on the walkers that
+// share its wavefront in the packed shapes -- a point would get other bits in a batch than alone (vamp_lnprob of one
+// point, the MAP search's candidates).
+template <int LPW>
+__device__ __forceinline__ bool group_any(bool pred) {
+    if constexpr (LPW == 64) return __any(pred);
+    else {
+        const int first = (int)(threadIdx.x & 63) & ~(LPW - 1);
+        return ((__ballot(pred) >> first) & ((1ull << LPW) - 1ull)) != 0ull;
+    }
+}
+
 // `tab` (TAB = true): the line's Taylor table replaces the near-axis rule for |z|^2 < 64
-template <int T, bool TAB = false>
+template <int T, bool TAB = false, int LPW = 64>
 __device__ __forceinline__ void tile_voigt(const LineRec& ln, const double* dtab, const double (&Xin)[T], double (&H)[T],
                                            const double* tab = nullptr, const double* ec = nullptr) {
     // ec: the exp constants in LDS (tile kernels with the far-field table) or null (literals)
@@ -611,9 +625,9 @@ __device__ __forceinline__ void tile_voigt(const LineRec& ln, const double* dtab
         return;
     }
 #endif
-    if (__any(lo < vamp::R2_M3)) {
-        if (__any(lo < vamp::R2_M4)) {
-            if (__any(lo < vamp::R2_CORE)) {
+    if (group_any<LPW>(lo < vamp::R2_M3)) {
+        if (group_any<LPW>(lo < vamp::R2_M4)) {
+            if (group_any<LPW>(lo < vamp::R2_CORE)) {
 #if VAMP_CORE_FASTPATH
                 // every pixel of the wavefront inside the zone (the usual case where a line is near): straight-line code,
                 // T independent chains with all their LDS reads in flight together.  Behind per-pixel branches (below:
@@ -622,7 +636,7 @@ __device__ __forceinline__ void tile_voigt(const LineRec& ln, const double* dtab
                 double hi = r2[0];
 #pragma unroll
                 for (int t = 1; t < T; ++t) hi = fmax(hi, r2[t]);
-                if (!__any(!(hi < vamp::R2_CORE))) {
+                if (!group_any<LPW>(!(hi < vamp::R2_CORE))) {
 #pragma unroll
                     for (int t = 0; t < T; ++t) {
                         if constexpr (TAB) H[t] = table_eval(tab, X[t]);
@@ -655,9 +669,9 @@ __device__ __forceinline__ void tile_voigt(const LineRec& ln, const double* dtab
         } else {
             tile_jfrac<4, T>(X, r2, y, H);
         }
-    } else if (__any(lo < vamp::R2_M2)) {
+    } else if (group_any<LPW>(lo < vamp::R2_M2)) {
         tile_jfrac<3, T>(X, r2, y, H);
-    } else if (__any(lo < vamp::R2_M1)) {
+    } else if (group_any<LPW>(lo < vamp::R2_M1)) {
         tile_jfrac<2, T>(X, r2, y, H);
     } else {
 #pragma unroll
@@ -719,7 +733,7 @@ __device__ __forceinline__ void sweep_range(const RegionDev& R, const typename P
                 double X[T], H[T];
 #pragma unroll
                 for (int t = 0; t < T; ++t) X[t] = fabs(xi[t] - ln.c) * ln.s;
-                tile_voigt<T, TAB>(ln, dtab_row<PK>(L, k), X, H, TAB ? tab + k * vamp::TAB_LINE : nullptr);
+                tile_voigt<T, TAB, PK::LPW>(ln, dtab_row<PK>(L, k), X, H, TAB ? tab + k * vamp::TAB_LINE : nullptr);
 #pragma unroll
                 for (int t = 0; t < T; ++t) tau[t] = fma(ln.amp, H[t], tau[t]);
             }
@@ -1098,19 +1112,19 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
 #endif
 
 // fp32 pixel arithmetic (Humlicek W4), chi^2 accumulated in fp64 (SURVEY section 7 hard parts).
-// Same shape as the fp64 sweep: TPIX pixels per lane in full tiles and one wave-uniform region per
-// (tile, line) -- region I when every lane has s >= 15, region II (valid for all s >= 5.5) when
-// every lane has s >= 5.5, per-lane selection only for tiles that touch the line core.
-template <int T>
+// Same shape as the fp64 sweep: TPIX pixels per lane in full tiles and one region per (tile, line) and walker
+// group (group_any) -- region I when every lane has s >= 15, region II (valid for all s >= 5.5) when every lane
+// has s >= 5.5, per-lane selection only for tiles that touch the line core.
+template <int T, int LPW = 64>
 __device__ __forceinline__ void tile_w4(float y, const float (&X)[T], float (&H)[T]) {
     float lo = X[0];
 #pragma unroll
     for (int t = 1; t < T; ++t) lo = fminf(lo, X[t]);
     lo += y;
-    if (!__any(!(lo >= 15.0f))) {
+    if (!group_any<LPW>(!(lo >= 15.0f))) {
 #pragma unroll
         for (int t = 0; t < T; ++t) H[t] = vamp::w4_region1(X[t], y);
-    } else if (!__any(!(lo >= 5.5f))) {
+    } else if (!group_any<LPW>(!(lo >= 5.5f))) {
 #pragma unroll
         for (int t = 0; t < T; ++t) H[t] = vamp::w4_region2(X[t], y);
     } else {
@@ -1189,7 +1203,7 @@ __device__ __forceinline__ void sweep_range_f32(const RegionDev& R, const typena
                 float X[T], H[T];
 #pragma unroll
                 for (int t = 0; t < T; ++t) X[t] = fabsf(xi[t] - c) * s;
-                tile_w4<T>(y, X, H);
+                tile_w4<T, PK::LPW>(y, X, H);
 #pragma unroll
                 for (int t = 0; t < T; ++t) tau[t] = fmaf(a, H[t], tau[t]);
             }
@@ -1606,7 +1620,7 @@ __device__ __forceinline__ double loglike_from_sum(const RegionDev& R, const LDS
 
 // log-posterior of the walker whose parameters sit in L.theta; `lane` = lane inside the walker's
 // group.  Groups of one wave may leave early independently: everything below communicates only
-// inside a group (xor shuffles with offsets < LPW) or through __any, which ignores inactive lanes.
+// inside a group (xor shuffles with offsets < LPW, group_any votes) or through __any, which ignores inactive lanes.
 template <bool F32, int MODE, class PK = PackWide>
 __device__ __forceinline__ double wave_lnprob(const RegionDev& R, typename PK::Lds& L, TileScratch& Sx, const double* dct,
                                               const PixPtrs& px, int lane, double* chi_out, int part, double* red, double* tab) {
@@ -2817,6 +2831,12 @@ int resident_waves_for(const vamp_ctx* c, int shape, long long movers) {
     else VAMP_FOR_MODE_PK(c->mode, shape, nw = resident_waves<false, M, PK>(movers));
     return nw;
 }
+// dynamic LDS bytes of a resident workgroup of shape PK with nw compute wavefronts (what launch_resident asks for)
+template <bool F32, int MODE, class PK>
+long long resident_lds(int nw) {
+    if constexpr (PK::SPLIT && PK::WPB > 1) return 0;
+    else return (long long)ResLayout<F32, MODE, PK>::total(nw);
+}
 // movers of one half-step launch of class `cl` on the launch-per-half-step path (what decides its shape)
 long long class_movers(const vamp_ctx* c, const LaunchClass& cl) {
     return c->n_regions == 1 ? c->W / 2 : (long long)cl.regions.size() * (c->W / 2);
@@ -3142,6 +3162,30 @@ int free_comm(vamp_ctx* c) {
 }  // namespace
 
 extern "C" {
+
+// Test hook, not part of the header: the resident workgroups run_resident would launch for the sampler's W, one row of
+// {class kind, compute wavefronts, walkers per round, dynamic LDS bytes} per launch class (at most max_classes rows).
+// Returns the number of classes, or an error code.
+long long vampdbg_resident_plan(vamp_ctx* c, int max_classes, long long* rows) {
+    if (!c || !rows || max_classes < 0) return fail(VAMP_ERR_ARG, "vampdbg_resident_plan: bad argument");
+    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vampdbg_resident_plan: call vamp_sampler_init first");
+    const long long halfW = c->W / 2;
+    const std::vector<LaunchClass>& classes = partition_for(c, halfW);
+    for (size_t ci = 0; ci < classes.size() && (int)ci < max_classes; ++ci) {
+        const LaunchClass& cl = classes[ci];
+        const int shape = class_shape(c, cl, halfW, class_movers(c, cl), true);
+        const int nw = resident_waves_for(c, shape, halfW);
+        long long lds = 0;
+        if (c->f32) VAMP_FOR_MODE_PK(c->mode, shape, lds = resident_lds<true, M, PK>(nw));
+        else VAMP_FOR_MODE_PK(c->mode, shape, lds = resident_lds<false, M, PK>(nw));
+        long long* row = rows + 4 * ci;
+        row[0] = cl.kind;
+        row[1] = nw;
+        row[2] = (long long)nw * (shape_walkers_per_block(shape) / shape_waves(shape));
+        row[3] = lds;
+    }
+    return (long long)classes.size();
+}
 
 int vamp_version(void) { return VAMP_ABI_VERSION; }
 
