@@ -255,6 +255,86 @@ def test_mixed_launch_classes_match_oracle():
         assert np.allclose(chains[0][r], chains[16][r], rtol=1e-10, atol=1e-12)
 
 
+def test_reused_context_equals_fresh_one():
+    """One context carried through the paths that grow or re-create its buffers gives, call by call, the bits of a
+    fresh context asked the same: vamp_lnprob from pinned host memory (<= 1 MB of theta), from device scratch (1.28 MB)
+    and pinned again; vamp_map_all after vamp_set_regions grew the context from one region to three;
+    vamp_sampler_half_step_ext with more movers than before; vamp_sampler_init of a larger ensemble, whose 16 384 movers
+    of a one-line region take the k_draws launch; and more than 4096 timed half-steps (one launch each, "resident" = 0)
+    between two reads of vamp_kernel_timing, all of them counted."""
+    import vamp_amd
+    g = load_golden("stretch_traj.npz")
+    x, f, n, X0 = g["x"], g["flux"], g["noise"], g["X0"]
+    rng = np.random.default_rng(11)
+
+    def walkers(W):
+        return X0[rng.integers(0, X0.shape[0], W)] * (1.0 + 1e-3 * rng.standard_normal((W, X0.shape[1])))
+
+    def fresh(xs=x, fs=f, ns=n):
+        c = vamp_amd.HipContext(device=0)
+        c.set_regions(xs, fs, ns, 1, mode=vamp_amd.MODE_VOIGT4)
+        return c
+
+    with fresh() as ctx:
+        for W in (8, 2000, 40000, 3):               # pinned, pinned grown, device scratch, pinned
+            th = walkers(W)
+            got = ctx.lnprob(th, return_chi2=True)
+            with fresh() as ref:
+                want = ref.lnprob(th, return_chi2=True)
+            assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got, want)), W
+
+        ctx.map_all([X0[0]], iterlim=60)
+        three = ([x, x, x[:-7]], [f, 0.98 * f + 0.02, f[:-7]], [n, n, n[:-7]])
+        ctx.set_regions(*three, 1, mode=vamp_amd.MODE_VOIGT4)
+        got = ctx.map_all(list(X0[:3]), iterlim=60)
+        with fresh(*three) as ref:
+            want = ref.map_all(list(X0[:3]), iterlim=60)
+        assert np.array_equal(np.concatenate(got[0]), np.concatenate(want[0]))
+        assert all(np.array_equal(a, b) for a, b in zip(got[1:], want[1:]))
+
+        ctx.set_regions(x, f, n, 1, mode=vamp_amd.MODE_VOIGT4)
+        assert ctx.region_classes() == ([3], 1)     # one- and two-line class: 16 384 movers take the k_draws launch
+        ctx.sampler_init(X0, seed=1, split_block=16)
+        for k in (2, 8):
+            perm = rng.permutation(16)
+            act, par = perm[:k], rng.choice(perm[8:], k)
+            zz, logu = (1.0 + rng.uniform(size=k)) ** 2 / 2.0, np.log(rng.uniform(size=k))
+            X, L, nacc, step = ctx.get_state()
+            ctx.half_step_ext(act, par, zz, logu)
+            with fresh() as ref:
+                ref.sampler_init(X0, seed=1, split_block=16)
+                ref.set_state(X, L, step)
+                ref.half_step_ext(act, par, zz, logu)
+                want = ref.get_state()
+            got = ctx.get_state()
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), k
+            assert np.array_equal(got[2] - nacc, want[2]), k
+
+        for W in (64, 32768):
+            th = walkers(W)
+            ctx.sampler_init(th, seed=5)
+            got = ctx.run(2)
+            with fresh() as ref:
+                ref.sampler_init(th, seed=5)
+                want = ref.run(2)
+            for key in ("chain", "lnprob", "n_accept"):
+                assert np.array_equal(got[key], want[key]), (W, key)
+
+        steps = 2100
+        ctx.set_option("resident", 0)
+        ctx.sampler_init(X0, seed=9, split_block=16)
+        ctx.kernel_timing(True)
+        got = ctx.run(steps, store_chain=False)
+        ms, launches = ctx.kernel_timing(False)
+        assert launches == 2 * steps and ms > 0
+        with fresh() as ref:
+            ref.set_option("resident", 0)
+            ref.sampler_init(X0, seed=9, split_block=16)
+            want = ref.run(steps, store_chain=False)
+            assert np.array_equal(got["n_accept"], want["n_accept"])
+            assert all(np.array_equal(a, b) for a, b in zip(ctx.get_state()[:2], ref.get_state()[:2]))
+
+
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_packed_launch_classes_at_production_size(dtype):
     """Automatic packing only packs launches of >= 16 384 walkers, so the production shapes of a

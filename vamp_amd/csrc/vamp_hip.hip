@@ -31,6 +31,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -2367,15 +2368,43 @@ int fail(int code, const std::string& msg) {
         }                                                                                     \
     } while (0)
 
-// device allocation released on every exit path of a host function
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
+// n elements of T in device memory (PINNED: page-locked host memory the kernels read and write directly), owned:
+// released by reset() and on destruction.  ensure(n) grows it to at least n elements, contents not kept; the capacity
+// is recorded only once the allocation has succeeded.
+template <class T, bool PINNED = false>
+class Buf {
+  public:
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    Buf(Buf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    ~Buf() { reset(); }
+    T* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset() {
+        if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    hipError_t ensure(size_t n) {
+        if (cap_ >= n) return hipSuccess;
+        reset();
+        void* p = nullptr;
+        const hipError_t e = PINNED ? hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, n * sizeof(T));
+        if (e != hipSuccess) return e;
+        p_ = static_cast<T*>(p);
+        cap_ = n;
+        return hipSuccess;
+    }
+  private:
+    T* p_ = nullptr;
+    size_t cap_ = 0;
 };
+template <class T> using DevBuf = Buf<T>;
+template <class T> using PinnedBuf = Buf<T, true>;
 
 // run the statement with `M` bound to the compile-time parameterisation that matches runtime
-// `mode` and `PK` to the packing (small = <16 lanes, 8 lines> per walker, else <64, 16>)
+// `mode`, `PK` to the Pack type of launch shape `shape` and `F32` to the context's precision
 #define VAMP_FOR_MODE_(mode, ...)                                               \
     do {                                                                        \
         if ((mode) == VAMP_GAUSS3) { constexpr int M = VAMP_GAUSS3; __VA_ARGS__; } \
@@ -2383,29 +2412,28 @@ struct DevBuf {
         else { constexpr int M = VAMP_NBZ3; __VA_ARGS__; }                      \
     } while (0)
 #define VAMP_FOR_MODE(mode, ...) VAMP_FOR_MODE_(mode, __VA_ARGS__)
+#define VAMP_FOR_F32(f32, ...)                                                  \
+    do {                                                                        \
+        if (f32) { constexpr bool F32 = true; __VA_ARGS__; }                    \
+        else { constexpr bool F32 = false; __VA_ARGS__; }                       \
+    } while (0)
 // launch shapes (see struct Pack): what one launch class of a context runs
 enum Shape { SH_SMALL = 0, SH_MID = 1, SH_WIDE = 2, SH_WIDE_FULL = 3, SH_SPLIT = 4, SH_SPLIT_FULL = 5, SH_SMALL2 = 6, SH_XL = 7 };
-#define VAMP_FOR_MODE_PK(mode, shape, ...)                                              \
+#define VAMP_FOR_PK(shape, ...)                                                 \
     do {                                                                        \
-        if ((shape) == SH_SMALL) { using PK = PackSmall; VAMP_FOR_MODE_(mode, __VA_ARGS__); } \
-        else if ((shape) == SH_SMALL2) { using PK = PackSmall2; VAMP_FOR_MODE_(mode, __VA_ARGS__); } \
-        else if ((shape) == SH_MID) { using PK = PackMid; VAMP_FOR_MODE_(mode, __VA_ARGS__); } \
-        else if ((shape) == SH_XL) { using PK = PackXL; VAMP_FOR_MODE_(mode, __VA_ARGS__); } \
-        else if ((shape) == SH_SPLIT_FULL) { using PK = PackSplitFull; VAMP_FOR_MODE_(mode, __VA_ARGS__); } \
-        else if ((shape) == SH_SPLIT) { using PK = PackSplit; VAMP_FOR_MODE_(mode, __VA_ARGS__); } \
-        else if ((shape) == SH_WIDE_FULL) { using PK = PackWideFull; VAMP_FOR_MODE_(mode, __VA_ARGS__); } \
-        else { using PK = PackWide; VAMP_FOR_MODE_(mode, __VA_ARGS__); }        \
+        if ((shape) == SH_SMALL) { using PK = PackSmall; __VA_ARGS__; }         \
+        else if ((shape) == SH_SMALL2) { using PK = PackSmall2; __VA_ARGS__; }  \
+        else if ((shape) == SH_MID) { using PK = PackMid; __VA_ARGS__; }        \
+        else if ((shape) == SH_XL) { using PK = PackXL; __VA_ARGS__; }          \
+        else if ((shape) == SH_SPLIT_FULL) { using PK = PackSplitFull; __VA_ARGS__; } \
+        else if ((shape) == SH_SPLIT) { using PK = PackSplit; __VA_ARGS__; }    \
+        else if ((shape) == SH_WIDE_FULL) { using PK = PackWideFull; __VA_ARGS__; } \
+        else { using PK = PackWide; __VA_ARGS__; }                              \
     } while (0)
-inline long long shape_walkers_per_block(int sh) {
-    return sh == SH_SMALL ? PackSmall::WALKERS_PER_BLOCK : sh == SH_SMALL2 ? PackSmall2::WALKERS_PER_BLOCK : sh == SH_MID ? PackMid::WALKERS_PER_BLOCK
-           : sh == SH_XL ? PackXL::WALKERS_PER_BLOCK : (sh == SH_SPLIT || sh == SH_SPLIT_FULL) ? 1 : PackWide::WALKERS_PER_BLOCK;
-}
-inline long long shape_waves(int sh) { return (long long)(sh == SH_SMALL ? PackSmall::WPB : sh == SH_SMALL2 ? PackSmall2::WPB : sh == SH_MID ? PackMid::WPB
-                                                           : sh == SH_XL ? PackXL::WPB : PackWide::WPB); }
-inline unsigned shape_threads(int sh) {
-    return sh == SH_SMALL ? PackSmall::THREADS : sh == SH_SMALL2 ? PackSmall2::THREADS : sh == SH_MID ? PackMid::THREADS
-           : sh == SH_XL ? PackXL::THREADS : (sh == SH_SPLIT || sh == SH_SPLIT_FULL) ? PackSplit::THREADS : PackWide::THREADS;
-}
+#define VAMP_FOR_MODE_PK(f32, mode, shape, ...) VAMP_FOR_F32(f32, VAMP_FOR_PK(shape, VAMP_FOR_MODE_(mode, __VA_ARGS__)))
+inline long long shape_walkers_per_block(int sh) { long long v = 0; VAMP_FOR_PK(sh, v = PK::WALKERS_PER_BLOCK); return v; }
+inline long long shape_waves(int sh) { long long v = 0; VAMP_FOR_PK(sh, v = PK::WPB); return v; }
+inline unsigned shape_threads(int sh) { unsigned v = 0; VAMP_FOR_PK(sh, v = PK::THREADS); return v; }
 
 // A launch class: the regions of a context that one kernel shape serves.  Real spectra mix many
 // short single-line regions (four walkers per wavefront) with a few long blends (a wavefront per
@@ -2414,7 +2442,57 @@ using vamp::plan::CK_SMALL; using vamp::plan::CK_MID; using vamp::plan::CK_WIDE;
 struct LaunchClass {
     int kind = CK_WIDE;
     std::vector<int> regions;
-    int* list_d = nullptr;       // device copy of `regions`; nullptr when the class is every region in order
+    DevBuf<int> list_d;          // device copy of `regions`; empty when the class is every region in order
+};
+
+// HIP event pairs around intervals of a stream's work (a half-step's launches, an exchange): begin() records an
+// interval's opening event, end() its closing one, flush() adds the closed intervals to ms and n.  At most 4096 pairs
+// are kept: begin() flushes a full set before it reuses them.
+struct EventPairs {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    size_t used = 0;             // closed intervals not yet flushed; ev[used] is the one begin() opened
+    double ms = 0.0;
+    long long n = 0;
+    EventPairs() = default;
+    EventPairs(const EventPairs&) = delete;
+    EventPairs& operator=(const EventPairs&) = delete;
+    ~EventPairs() {
+        for (auto& p : ev) {
+            (void)hipEventDestroy(p.first);
+            (void)hipEventDestroy(p.second);
+        }
+    }
+    int begin(hipStream_t st) {
+        if (used == ev.size()) {
+            if (ev.size() >= 4096) {
+                int rc = flush();
+                if (rc) return rc;
+            } else {
+                hipEvent_t a, b;
+                HIP_TRY(hipEventCreate(&a));
+                HIP_TRY(hipEventCreate(&b));
+                ev.emplace_back(a, b);
+            }
+        }
+        HIP_TRY(hipEventRecord(ev[used].first, st));
+        return 0;
+    }
+    int end(hipStream_t st) {
+        HIP_TRY(hipEventRecord(ev[used].second, st));
+        ++used;
+        return 0;
+    }
+    int flush() {
+        for (size_t i = 0; i < used; ++i) {
+            float t = 0.f;
+            HIP_TRY(hipEventSynchronize(ev[i].second));
+            HIP_TRY(hipEventElapsedTime(&t, ev[i].first, ev[i].second));
+            ms += t;
+            n += 1;
+        }
+        used = 0;
+        return 0;
+    }
 };
 
 }  // namespace
@@ -2439,9 +2517,8 @@ struct vamp_ctx {
     std::vector<LaunchClass> classes_small;
     std::vector<int> class_of_small;
     // draws of packed launches (k_draws), grown on demand
-    int *dr_ws = nullptr, *dr_wc = nullptr;
-    double *dr_z = nullptr, *dr_lu = nullptr, *dr_lz = nullptr;
-    long long dr_cap = 0;
+    DevBuf<int> dr_ws, dr_wc;
+    DevBuf<double> dr_z, dr_lu, dr_lz;
     // launch classes of one half-step run concurrently, each on its own stream (forked from and joined
     // to the ctx stream with events): a class of low-occupancy blends and a class of register-bound
     // short regions fill each other's stalls
@@ -2450,10 +2527,10 @@ struct vamp_ctx {
     hipEvent_t ev_fork = nullptr;
     std::vector<hipEvent_t> ev_join;
     std::vector<RegionDev> regions_h;
-    RegionDev* regions_d = nullptr;
+    DevBuf<RegionDev> regions_d;
     long long n_pix = 0;
-    double *x_d = nullptr, *f_d = nullptr, *wt_d = nullptr;
-    float *xf_d = nullptr, *ff_d = nullptr, *wtf_d = nullptr;
+    DevBuf<double> x_d, f_d, wt_d;
+    DevBuf<float> xf_d, ff_d, wtf_d;
     // sampler
     bool sampler_ready = false;
     long long W = 0, total_theta = 0, total_walkers = 0;
@@ -2461,16 +2538,18 @@ struct vamp_ctx {
     double a = 2.0;
     unsigned long long seed = 0;
     long long step = 0;
+    // the state: X_d / lnp_d are the walkers' positions and lnprobs, in X_own / lnp_own or in the caller's memory
+    // (vamp_sampler_bind_state)
     double* X_d = nullptr;
     double* lnp_d = nullptr;
-    bool X_ext = false;
-    long long* nacc_d = nullptr;
+    DevBuf<double> X_own, lnp_own;
+    DevBuf<long long> nacc_d;
     long long slot_begin = 0, slot_end = 0;      // part 0 (the whole share when shard_parts == 1)
     int shard_rank = 0, shard_world = 1, shard_parts = 1;
     long long part_slots = 0, part_stride = 0;   // slots per part; distance between this rank's parts
     // walker-sharded runs: active-colour exchange (pack -> all-gather -> scatter), see vamp_comm_*
-    double* send_d = nullptr;        // [parts][part_slots][D + 1]
-    double* recv_d = nullptr;        // [parts][world * part_slots][D + 1]
+    DevBuf<double> send_d;           // [parts][part_slots][D + 1]
+    DevBuf<double> recv_d;           // [parts][world * part_slots][D + 1]
     std::vector<unsigned> part_step; // (step, half) of the last launch of every part
     std::vector<int> part_half;
     void* comm = nullptr;            // ncclComm_t (RCCL), one per ctx
@@ -2478,100 +2557,52 @@ struct vamp_ctx {
     hipStream_t comm_stream = nullptr;
     std::vector<hipEvent_t> ev_kernel, ev_scatter;   // per part: kernel done / rows scattered
     // exchange timing (vamp_exchange_timing): event pairs around all-gather + scatter on the stream they run on
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> xev;
-    size_t xev_used = 0;
-    double xtiming_ms = 0.0;
-    long long xtiming_n = 0;
+    EventPairs xtiming;
     // grow-only scratch of vamp_lnprob (the MAP optimiser calls it thousands of times with W = 1)
-    double *sc_th = nullptr, *sc_lp = nullptr, *sc_chi = nullptr;
-    size_t sc_th_cap = 0, sc_w_cap = 0;
+    DevBuf<double> sc_th, sc_lp, sc_chi;
     // small evaluations (the MAP searches: a few points per region, thousands of times): pinned host memory the
     // kernel reads and writes directly -- no staging copies, one launch and one synchronisation per call
-    double *pin_th = nullptr, *pin_out = nullptr;
-    size_t pin_th_cap = 0, pin_out_cap = 0;
+    PinnedBuf<double> pin_th, pin_out;
     // the MAP searches on the device (k_map_search): start points, flags, simplices, results; grow-only
-    double *map_th_d = nullptr, *map_best_d = nullptr, *map_sim_d = nullptr;
-    unsigned char* map_act_d = nullptr;
-    long long* map_it_d = nullptr;
-    size_t map_th_cap = 0, map_sim_cap = 0, map_r_cap = 0;
+    DevBuf<double> map_th_d, map_best_d, map_sim_d;
+    DevBuf<unsigned char> map_act_d;
+    DevBuf<long long> map_it_d;
     // run-time options (vamp_ctx_set_option)
     int opt_map_device = 1;          // 1: vamp_map_all runs k_map_search; 0: the host-driven search, one launch per iteration
     int opt_resident = 1;            // 1: small ensembles are stepped by the device-resident loop where it pays (resident_eligible);
                                      // 0: never; 2: wherever the kernel can run
     // scratch for the ext hook
-    int *ext_act_d = nullptr, *ext_par_d = nullptr;
-    double *ext_z_d = nullptr, *ext_lu_d = nullptr;
-    long long ext_cap = 0;
-    // kernel timing
+    DevBuf<int> ext_act_d, ext_par_d;
+    DevBuf<double> ext_z_d, ext_lu_d;
+    // kernel timing: one interval per launch_half / run_resident call
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-    size_t ev_used = 0;
-    double timing_ms = 0.0;
-    long long timing_launches = 0;
+    EventPairs ktiming;
 
-    PixPtrs pix() const { return PixPtrs{x_d, f_d, wt_d, xf_d, ff_d, wtf_d}; }
+    PixPtrs pix() const { return PixPtrs{x_d.get(), f_d.get(), wt_d.get(), xf_d.get(), ff_d.get(), wtf_d.get()}; }
 };
 
 namespace {
 
-int free_regions(vamp_ctx* c) {
-    for (void* p : {(void*)c->regions_d, (void*)c->x_d, (void*)c->f_d, (void*)c->wt_d, (void*)c->xf_d, (void*)c->ff_d,
-                    (void*)c->wtf_d})
-        if (p) (void)hipFree(p);
-    for (std::vector<LaunchClass>* part : {&c->classes, &c->classes_small}) {
-        for (LaunchClass& cl : *part)
-            if (cl.list_d) (void)hipFree(cl.list_d);
-        part->clear();
-    }
+// forgets the regions and their launch classes
+void reset_regions(vamp_ctx* c) {
+    c->regions_d.reset();
+    c->x_d.reset(); c->f_d.reset(); c->wt_d.reset();
+    c->xf_d.reset(); c->ff_d.reset(); c->wtf_d.reset();
+    c->classes.clear();
+    c->classes_small.clear();
     c->class_of.clear();
     c->class_of_small.clear();
-    c->regions_d = nullptr;
-    c->x_d = c->f_d = c->wt_d = nullptr;
-    c->xf_d = c->ff_d = c->wtf_d = nullptr;
     c->n_regions = 0;
     c->regions_h.clear();
-    return 0;
 }
 
-int free_sampler(vamp_ctx* c) {
-    if (c->X_d && !c->X_ext) (void)hipFree(c->X_d);
-    if (c->lnp_d && !c->X_ext) (void)hipFree(c->lnp_d);
-    if (c->nacc_d) (void)hipFree(c->nacc_d);
-    if (c->send_d) (void)hipFree(c->send_d);
-    if (c->recv_d) (void)hipFree(c->recv_d);
-    c->send_d = c->recv_d = nullptr;
-    c->X_d = nullptr;
-    c->lnp_d = nullptr;
-    c->nacc_d = nullptr;
+// forgets the state, also a bound one (vamp_sampler_bind_state)
+void reset_sampler(vamp_ctx* c) {
+    c->X_own.reset(); c->lnp_own.reset();
+    c->X_d = c->lnp_d = nullptr;
+    c->nacc_d.reset();
+    c->send_d.reset(); c->recv_d.reset();
     c->sampler_ready = false;
-    return 0;
-}
-
-int flush_timing(vamp_ctx* c) {
-    if (c->ev_used == 0) return 0;
-    HIP_TRY(hipEventSynchronize(c->ev[c->ev_used - 1].second));
-    for (size_t i = 0; i < c->ev_used; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[i].first, c->ev[i].second));
-        c->timing_ms += ms;
-        c->timing_launches += 1;
-    }
-    c->ev_used = 0;
-    return 0;
-}
-
-int flush_exchange_timing(vamp_ctx* c) {
-    if (c->xev_used == 0) return 0;
-    HIP_TRY(hipEventSynchronize(c->xev[c->xev_used - 1].second));
-    for (size_t i = 0; i < c->xev_used; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventSynchronize(c->xev[i].second));
-        HIP_TRY(hipEventElapsedTime(&ms, c->xev[i].first, c->xev[i].second));
-        c->xtiming_ms += ms;
-        c->xtiming_n += 1;
-    }
-    c->xev_used = 0;
-    return 0;
 }
 
 // exchange buffers of the shard set by vamp_sampler_set_shard_parts: the movers of every part in slot order,
@@ -2579,8 +2610,8 @@ int flush_exchange_timing(vamp_ctx* c) {
 int ensure_part_events(vamp_ctx* c, int parts);
 int alloc_exchange_buffers(vamp_ctx* c) {
     const int D = c->regions_h[0].D;
-    HIP_TRY(hipMalloc(&c->send_d, vamp::plan::exchange_send_doubles(c->shard_parts, c->part_slots, D) * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->recv_d, vamp::plan::exchange_recv_doubles(c->shard_parts, c->shard_world, c->part_slots, D) * sizeof(double)));
+    HIP_TRY(c->send_d.ensure(vamp::plan::exchange_send_doubles(c->shard_parts, c->part_slots, D)));
+    HIP_TRY(c->recv_d.ensure(vamp::plan::exchange_recv_doubles(c->shard_parts, c->shard_world, c->part_slots, D)));
     c->part_step.assign(c->shard_parts, 0u);
     c->part_half.assign(c->shard_parts, 0);
     if (c->comm) return ensure_part_events(c, c->shard_parts);
@@ -2634,27 +2665,11 @@ int class_shape(const vamp_ctx* c, const LaunchClass& cl, long long per_region, 
     return c->full_tiles ? SH_WIDE_FULL : SH_WIDE;
 }
 
-int ensure_draw_buffers(vamp_ctx* c, long long n) {
-    if (c->dr_cap >= n) return 0;
-    for (void* p : {(void*)c->dr_ws, (void*)c->dr_wc, (void*)c->dr_z, (void*)c->dr_lu, (void*)c->dr_lz})
-        if (p) (void)hipFree(p);
-    c->dr_ws = c->dr_wc = nullptr;
-    c->dr_z = c->dr_lu = c->dr_lz = nullptr;
-    c->dr_cap = 0;
-    HIP_TRY(hipMalloc(&c->dr_ws, n * sizeof(int)));
-    HIP_TRY(hipMalloc(&c->dr_wc, n * sizeof(int)));
-    HIP_TRY(hipMalloc(&c->dr_z, n * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->dr_lu, n * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->dr_lz, n * sizeof(double)));
-    c->dr_cap = n;
-    return 0;
-}
-
-// One half-step of this ctx's share (piece `part` of it): one launch per launch class, on the ctx
-// stream.  ext: host-supplied draws for `ext_n` movers of `ext_region`.
-int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n, int part = 0) {
+// the SamplerDev fields every sampler launch shares, the others zero
+SamplerDev sampler_dev(const vamp_ctx* c) {
     SamplerDev S;
-    S.regions = c->regions_d;
+    std::memset(&S, 0, sizeof(S));
+    S.regions = c->regions_d.get();
     S.n_regions = c->n_regions;
     S.W = c->W;
     S.split_block = c->split_block;
@@ -2662,33 +2677,45 @@ int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n
     S.seed = c->seed;
     S.X = c->X_d;
     S.lnp = c->lnp_d;
-    S.n_accept = c->nacc_d;
-    S.region_list = nullptr;
-    S.slot_begin = S.slot_end = 0;
-    S.wpr = S.bpr = S.n_cls_regions = 0;
-    S.pack = (!ext && c->send_d) ? c->send_d + (long long)part * c->part_slots * (c->regions_h[0].D + 1) : nullptr;
+    S.n_accept = c->nacc_d.get();
+    return S;
+}
+
+// the launch classes of a half-step (launch_half, run_resident) on forked streams: class 0 runs on the ctx stream,
+// class ci > 0 on cls_stream[ci - 1], which starts at the fork point recorded here on the ctx stream ...
+int fork_classes(vamp_ctx* c, size_t ncls) {
+    while (c->cls_stream.size() < ncls - 1) {
+        hipStream_t st;
+        hipEvent_t ev;
+        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        c->cls_stream.push_back(st);
+        c->ev_join.push_back(ev);
+    }
+    if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+    for (size_t ci = 1; ci < ncls; ++ci) HIP_TRY(hipStreamWaitEvent(c->cls_stream[ci - 1], c->ev_fork, 0));
+    return 0;
+}
+// ... and which the ctx stream waits for again once class ci is launched
+int join_class(vamp_ctx* c, size_t ci) {
+    if (ci == 0) return 0;
+    HIP_TRY(hipEventRecord(c->ev_join[ci - 1], c->cls_stream[ci - 1]));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join[ci - 1], 0));
+    return 0;
+}
+
+// One half-step of this ctx's share (piece `part` of it): one launch per launch class, on the ctx
+// stream.  ext: host-supplied draws for `ext_n` movers of `ext_region`.
+int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n, int part = 0) {
+    SamplerDev S = sampler_dev(c);
     if (!ext && c->send_d) {
+        S.pack = c->send_d.get() + (long long)part * c->part_slots * (c->regions_h[0].D + 1);
         c->part_step[part] = (unsigned)c->step;
         c->part_half[part] = half;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        if (c->ev_used == c->ev.size()) {
-            if (c->ev.size() >= 4096) {
-                int rc = flush_timing(c);
-                if (rc) return rc;
-            } else {
-                hipEvent_t a, b;
-                HIP_TRY(hipEventCreate(&a));
-                HIP_TRY(hipEventCreate(&b));
-                c->ev.emplace_back(a, b);
-            }
-        }
-        e0 = c->ev[c->ev_used].first;
-        e1 = c->ev[c->ev_used].second;
-        c->ev_used++;
-        HIP_TRY(hipEventRecord(e0, c->stream));
-    }
+    int rc = c->timing ? c->ktiming.begin(c->stream) : 0;
+    if (rc) return rc;
     const unsigned step = (unsigned)c->step;
     const PixPtrs px = c->pix();
     const long long halfW = c->W / 2;
@@ -2704,18 +2731,8 @@ int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n
     // 4.20 ms); for the small ensembles of a ladder the event traffic of fork and join costs more than it hides
     // (q1422 ladder, first rung: 73 -> 57 us per half-step without it)
     const bool fork = !ext && ncls > 1 && c->concurrent_classes && c->total_walkers / 2 >= PACK_MIN_WALKERS * 4;
-    if (fork) {
-        while (c->cls_stream.size() < ncls - 1) {
-            hipStream_t st;
-            hipEvent_t ev;
-            HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            c->cls_stream.push_back(st);
-            c->ev_join.push_back(ev);
-        }
-        if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    }
+    rc = fork ? fork_classes(c, ncls) : 0;
+    if (rc) return rc;
     // draws of the packed classes: one slice of the buffers per class (the classes may overlap in time)
     long long draw_total = 0;
     if (!ext)
@@ -2737,12 +2754,8 @@ int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n
             n = S.slot_end;
         }
         if (n <= 0) continue;
-        hipStream_t st = c->stream;
-        if (fork && ci > 0) {
-            st = c->cls_stream[ci - 1];
-            HIP_TRY(hipStreamWaitEvent(st, c->ev_fork, 0));
-        }
-        S.region_list = cl.list_d;
+        const hipStream_t st = (fork && ci > 0) ? c->cls_stream[ci - 1] : c->stream;
+        S.region_list = cl.list_d.get();
         // (a shard or a piece of a single-region ensemble takes the shape of the WHOLE ensemble)
         const int shape = class_shape(c, cl, ext ? n : halfW, (!ext && c->n_regions == 1) ? halfW : n, packable);
         unsigned grid = (unsigned)((n + shape_walkers_per_block(shape) - 1) / shape_walkers_per_block(shape));
@@ -2760,46 +2773,35 @@ int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n
         }
         const dim3 threads(shape_threads(shape));
         if (ext) {
-            if (c->f32)
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_half_step<true, DRAW_HOST, M, PK>), dim3(grid), threads, 0, st, S, px, step,
-                                                          half, ext_region, ext_n, c->ext_act_d, c->ext_par_d, c->ext_z_d, c->ext_lu_d, nd));
-            else
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_half_step<false, DRAW_HOST, M, PK>), dim3(grid), threads, 0, st, S, px, step,
-                                                          half, ext_region, ext_n, c->ext_act_d, c->ext_par_d, c->ext_z_d, c->ext_lu_d, nd));
+            VAMP_FOR_MODE_PK(c->f32, c->mode, shape, hipLaunchKernelGGL((k_half_step<F32, DRAW_HOST, M, PK>), dim3(grid), threads, 0, st, S, px, step,
+                                                                    half, ext_region, ext_n, c->ext_act_d.get(), c->ext_par_d.get(),
+                                                                    c->ext_z_d.get(), c->ext_lu_d.get(), nd));
         } else if (!small_ensemble(halfW) && (shape == SH_SMALL || shape == SH_SMALL2 || (shape == SH_MID && VAMP_MID_PREDRAW))) {
             // four walkers per wavefront (or a walker per wavefront at ~1.7 wavefronts per SIMD, where
             // ~1000 scalar instructions of draws are exposed latency): draws in their own
             // one-thread-per-mover launch -- for ensembles that fill the chip; a small ensemble's half-step is bound by
             // its launches, and draws in the kernel are one launch less (the same draws: same keys, same functions)
-            int rc = ensure_draw_buffers(c, draw_total);
-            if (rc) return rc;
-            int *d_ws = c->dr_ws + draw_off, *d_wc = c->dr_wc + draw_off;
-            double *d_z = c->dr_z + draw_off, *d_lu = c->dr_lu + draw_off, *d_lz = c->dr_lz + draw_off;
+            HIP_TRY(c->dr_ws.ensure(draw_total));
+            HIP_TRY(c->dr_wc.ensure(draw_total));
+            HIP_TRY(c->dr_z.ensure(draw_total));
+            HIP_TRY(c->dr_lu.ensure(draw_total));
+            HIP_TRY(c->dr_lz.ensure(draw_total));
+            int *d_ws = c->dr_ws.get() + draw_off, *d_wc = c->dr_wc.get() + draw_off;
+            double *d_z = c->dr_z.get() + draw_off, *d_lu = c->dr_lu.get() + draw_off, *d_lz = c->dr_lz.get() + draw_off;
             draw_off += n;
             hipLaunchKernelGGL(k_draws, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, step, half, n, d_ws, d_wc, d_z, d_lu, d_lz);
             HIP_TRY(hipGetLastError());
-            if (c->f32)
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_half_step<true, DRAW_PRE, M, PK>), dim3(grid), threads, 0, st, S, px, step,
-                                                          half, 0, 0ll, d_ws, d_wc, d_z, d_lu, d_lz));
-            else
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_half_step<false, DRAW_PRE, M, PK>), dim3(grid), threads, 0, st, S, px, step,
-                                                          half, 0, 0ll, d_ws, d_wc, d_z, d_lu, d_lz));
+            VAMP_FOR_MODE_PK(c->f32, c->mode, shape, hipLaunchKernelGGL((k_half_step<F32, DRAW_PRE, M, PK>), dim3(grid), threads, 0, st, S, px, step,
+                                                                    half, 0, 0ll, d_ws, d_wc, d_z, d_lu, d_lz));
         } else {
-            if (c->f32)
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_half_step<true, DRAW_INLINE, M, PK>), dim3(grid), threads, 0, st, S, px, step,
-                                                          half, 0, 0ll, ni, ni, nd, nd, nd));
-            else
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_half_step<false, DRAW_INLINE, M, PK>), dim3(grid), threads, 0, st, S, px, step,
-                                                          half, 0, 0ll, ni, ni, nd, nd, nd));
+            VAMP_FOR_MODE_PK(c->f32, c->mode, shape, hipLaunchKernelGGL((k_half_step<F32, DRAW_INLINE, M, PK>), dim3(grid), threads, 0, st, S, px, step,
+                                                                    half, 0, 0ll, ni, ni, nd, nd, nd));
         }
         HIP_TRY(hipGetLastError());
-        if (fork && ci > 0) {
-            HIP_TRY(hipEventRecord(c->ev_join[ci - 1], st));
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join[ci - 1], 0));
-        }
+        rc = fork ? join_class(c, ci) : 0;
+        if (rc) return rc;
     }
-    if (c->timing) HIP_TRY(hipEventRecord(e1, c->stream));
-    return 0;
+    return c->timing ? c->ktiming.end(c->stream) : 0;
 }
 
 // ---- the device-resident step loop (k_run_resident): eligibility and launch ----------------------------------------
@@ -2814,21 +2816,33 @@ int resident_waves(long long movers) {
     }
 }
 template <bool F32, int MODE, class PK>
-void launch_resident(dim3 grid, dim3 threads, int nw, hipStream_t st, const SamplerDev& S, const PixPtrs& px, unsigned step0, long long n_steps,
-                     int thin, double* chain_dev, double* lchain_dev, long long total_theta, long long total_walkers) {
+int launch_resident(int device, dim3 grid, dim3 threads, int nw, hipStream_t st, const SamplerDev& S, const PixPtrs& px, unsigned step0,
+                    long long n_steps, int thin, double* chain_dev, double* lchain_dev, long long total_theta, long long total_walkers) {
     if constexpr (!(PK::SPLIT && PK::WPB > 1)) {    // (resident_waves is 0 for the workgroup-per-walker shapes: never launched)
         using LY = ResLayout<F32, MODE, PK>;
         const size_t lds = LY::total(nw);
-        if (lds > 48 * 1024)        // beyond the default dynamic allocation: the kernel is told once per process
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_run_resident<F32, MODE, PK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RES_MAX_LDS);
+        // beyond the default dynamic allocation the kernel must be told, once per device (bit d of `told`: device d)
+        static std::atomic<unsigned long long> told{0};
+        const unsigned long long bit = device < 64 ? 1ull << device : 0ull;
+        if (lds > 48 * 1024 && !(told.load() & bit)) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_run_resident<F32, MODE, PK>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)RES_MAX_LDS);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(VAMP_ERR_HIP, "hipFuncSetAttribute(k_run_resident<F32=" + std::to_string(F32) + ", MODE=" + std::to_string(MODE) +
+                                              ", LPW=" + std::to_string(PK::LPW) + ", WPB=" + std::to_string(PK::WPB) + ">, " +
+                                              "MaxDynamicSharedMemorySize, " + std::to_string(RES_MAX_LDS) + " bytes): " + hipGetErrorString(e));
+            }
+            told.fetch_or(bit);
+        }
         hipLaunchKernelGGL((k_run_resident<F32, MODE, PK>), grid, threads, lds, st, S, px, step0, n_steps, thin, chain_dev, lchain_dev,
                            total_theta, total_walkers);
     }
+    return 0;
 }
 int resident_waves_for(const vamp_ctx* c, int shape, long long movers) {
     int nw = 0;
-    if (c->f32) VAMP_FOR_MODE_PK(c->mode, shape, nw = resident_waves<true, M, PK>(movers));
-    else VAMP_FOR_MODE_PK(c->mode, shape, nw = resident_waves<false, M, PK>(movers));
+    VAMP_FOR_MODE_PK(c->f32, c->mode, shape, nw = resident_waves<F32, M, PK>(movers));
     return nw;
 }
 // dynamic LDS bytes of a resident workgroup of shape PK with nw compute wavefronts (what launch_resident asks for)
@@ -2864,71 +2878,33 @@ bool resident_eligible(const vamp_ctx* c) {
 }
 // n_steps of every region, one launch per launch class (the classes on forked streams, as in launch_half)
 int run_resident(vamp_ctx* c, long long n_steps, int thin, double* chain_dev, double* lchain_dev) {
-    SamplerDev S;
-    std::memset(&S, 0, sizeof(S));
-    S.regions = c->regions_d;
-    S.n_regions = c->n_regions;
-    S.W = c->W;
-    S.split_block = c->split_block;
-    S.a = c->a;
-    S.seed = c->seed;
-    S.X = c->X_d;
-    S.lnp = c->lnp_d;
-    S.n_accept = c->nacc_d;
+    SamplerDev S = sampler_dev(c);
     const long long halfW = c->W / 2;
     const std::vector<LaunchClass>& classes = partition_for(c, halfW);
     const size_t ncls = classes.size();
     const bool fork = ncls > 1 && c->concurrent_classes;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        if (c->ev_used == c->ev.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            c->ev.emplace_back(a, b);
-        }
-        e0 = c->ev[c->ev_used].first;
-        e1 = c->ev[c->ev_used].second;
-        c->ev_used++;
-        HIP_TRY(hipEventRecord(e0, c->stream));
-    }
-    if (fork) {
-        while (c->cls_stream.size() < ncls - 1) {
-            hipStream_t st;
-            hipEvent_t ev;
-            HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            c->cls_stream.push_back(st);
-            c->ev_join.push_back(ev);
-        }
-        if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    }
+    int rc = c->timing ? c->ktiming.begin(c->stream) : 0;
+    if (rc) return rc;
+    rc = fork ? fork_classes(c, ncls) : 0;
+    if (rc) return rc;
     const PixPtrs px = c->pix();
     for (size_t ci = 0; ci < ncls; ++ci) {
         const LaunchClass& cl = classes[ci];
-        hipStream_t st = c->stream;
-        if (fork && ci > 0) {
-            st = c->cls_stream[ci - 1];
-            HIP_TRY(hipStreamWaitEvent(st, c->ev_fork, 0));
-        }
-        S.region_list = cl.list_d;
+        const hipStream_t st = (fork && ci > 0) ? c->cls_stream[ci - 1] : c->stream;
+        S.region_list = cl.list_d.get();
         const int shape = class_shape(c, cl, halfW, class_movers(c, cl), true);     // the shape launch_half runs this class in
         const int nw = resident_waves_for(c, shape, halfW);
         const dim3 grid((unsigned)cl.regions.size()), threads(64u * (unsigned)(nw + 1));
-        if (c->f32)
-            VAMP_FOR_MODE_PK(c->mode, shape, (launch_resident<true, M, PK>(grid, threads, nw, st, S, px, (unsigned)c->step, n_steps, thin, chain_dev,
-                                                                          lchain_dev, c->total_theta, c->total_walkers)));
-        else
-            VAMP_FOR_MODE_PK(c->mode, shape, (launch_resident<false, M, PK>(grid, threads, nw, st, S, px, (unsigned)c->step, n_steps, thin, chain_dev,
-                                                                           lchain_dev, c->total_theta, c->total_walkers)));
+        VAMP_FOR_MODE_PK(c->f32, c->mode, shape, rc = launch_resident<F32, M, PK>(c->device, grid, threads, nw, st, S, px, (unsigned)c->step,
+                                                                                 n_steps, thin, chain_dev, lchain_dev, c->total_theta,
+                                                                                 c->total_walkers));
+        if (rc) return rc;
         HIP_TRY(hipGetLastError());
-        if (fork && ci > 0) {
-            HIP_TRY(hipEventRecord(c->ev_join[ci - 1], st));
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join[ci - 1], 0));
-        }
+        rc = fork ? join_class(c, ci) : 0;
+        if (rc) return rc;
     }
-    if (c->timing) HIP_TRY(hipEventRecord(e1, c->stream));
+    rc = c->timing ? c->ktiming.end(c->stream) : 0;
+    if (rc) return rc;
     c->step += n_steps;
     return 0;
 }
@@ -3056,20 +3032,10 @@ struct RoctxRange {
 
 // rows of part `part` gathered in c->recv_d -> walker rows (on `st`)
 int launch_scatter(vamp_ctx* c, int part, hipStream_t st) {
-    SamplerDev S;
-    std::memset(&S, 0, sizeof(S));
-    S.regions = c->regions_d;
-    S.n_regions = c->n_regions;
-    S.W = c->W;
-    S.split_block = c->split_block;
-    S.a = c->a;
-    S.seed = c->seed;
-    S.X = c->X_d;
-    S.lnp = c->lnp_d;
-    S.n_accept = c->nacc_d;
+    const SamplerDev S = sampler_dev(c);
     const long long n_rows = (long long)c->shard_world * c->part_slots;
     const long long own_lo = (long long)c->shard_rank * c->part_slots;
-    const double* recv = c->recv_d + (long long)part * n_rows * (c->regions_h[0].D + 1);
+    const double* recv = c->recv_d.get() + (long long)part * n_rows * (c->regions_h[0].D + 1);
     const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
     hipLaunchKernelGGL(k_scatter_rows, dim3(grid), dim3(256), 0, st, S, recv, c->part_step[part], c->part_half[part],
                        (long long)part * c->part_stride, n_rows, own_lo, own_lo + c->part_slots);
@@ -3085,8 +3051,8 @@ int exchange_part(vamp_ctx* c, int part) {
     if (rc) return rc;
     const long long row = c->regions_h[0].D + 1;
     const size_t count = (size_t)(c->part_slots * row);
-    const double* send = c->send_d + (long long)part * c->part_slots * row;
-    double* recv = c->recv_d + (long long)part * c->shard_world * c->part_slots * row;
+    const double* send = c->send_d.get() + (long long)part * c->part_slots * row;
+    double* recv = c->recv_d.get() + (long long)part * c->shard_world * c->part_slots * row;
     const bool overlap = c->shard_parts > 1;
     hipStream_t st = overlap ? c->comm_stream : c->stream;
     if (overlap) {
@@ -3095,33 +3061,14 @@ int exchange_part(vamp_ctx* c, int part) {
         HIP_TRY(hipEventRecord(c->ev_kernel[part], c->stream));
         HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_kernel[part], 0));
     }
-    hipEvent_t x1 = nullptr;
-    if (c->timing) {
-        if (c->xev_used == c->xev.size()) {
-            if (c->xev.size() >= 4096) {
-                rc = flush_exchange_timing(c);
-                if (rc) return rc;
-            } else {
-                hipEvent_t a, b;
-                HIP_TRY(hipEventCreate(&a));
-                HIP_TRY(hipEventCreate(&b));
-                c->xev.emplace_back(a, b);
-            }
-        }
-        HIP_TRY(hipEventRecord(c->xev[c->xev_used].first, st));
-        x1 = c->xev[c->xev_used].second;
-        c->xev_used++;
-    }
-    {
-        const int r_ = api->AllGather(send, recv, count, RCCL_FLOAT64, c->comm, st);
-        if (r_ == 0) rc = launch_scatter(c, part, st);
-        if (r_ != 0 || rc) {
-            if (x1) c->xev_used--;              // its closing event will never be recorded
-            if (r_ != 0) return fail(VAMP_ERR_COMM, std::string("ncclAllGather: ") + api->GetErrorString(r_));
-            return rc;
-        }
-    }
-    if (x1) HIP_TRY(hipEventRecord(x1, st));
+    rc = c->timing ? c->xtiming.begin(st) : 0;
+    if (rc) return rc;
+    const int r_ = api->AllGather(send, recv, count, RCCL_FLOAT64, c->comm, st);
+    if (r_ != 0) return fail(VAMP_ERR_COMM, std::string("ncclAllGather: ") + api->GetErrorString(r_));
+    rc = launch_scatter(c, part, st);
+    if (rc) return rc;
+    rc = c->timing ? c->xtiming.end(st) : 0;
+    if (rc) return rc;
     if (overlap) HIP_TRY(hipEventRecord(c->ev_scatter[part], c->comm_stream));
     return 0;
 }
@@ -3176,8 +3123,7 @@ long long vampdbg_resident_plan(vamp_ctx* c, int max_classes, long long* rows) {
         const int shape = class_shape(c, cl, halfW, class_movers(c, cl), true);
         const int nw = resident_waves_for(c, shape, halfW);
         long long lds = 0;
-        if (c->f32) VAMP_FOR_MODE_PK(c->mode, shape, lds = resident_lds<true, M, PK>(nw));
-        else VAMP_FOR_MODE_PK(c->mode, shape, lds = resident_lds<false, M, PK>(nw));
+        VAMP_FOR_MODE_PK(c->f32, c->mode, shape, lds = resident_lds<F32, M, PK>(nw));
         long long* row = rows + 4 * ci;
         row[0] = cl.kind;
         row[1] = nw;
@@ -3230,28 +3176,11 @@ int vamp_ctx_destroy(vamp_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
     free_comm(c);
-    free_sampler(c);
-    free_regions(c);
-    for (void* p : {(void*)c->ext_act_d, (void*)c->ext_par_d, (void*)c->ext_z_d, (void*)c->ext_lu_d, (void*)c->sc_th,
-                    (void*)c->sc_lp, (void*)c->sc_chi, (void*)c->dr_ws, (void*)c->dr_wc, (void*)c->dr_z, (void*)c->dr_lu,
-                    (void*)c->dr_lz, (void*)c->map_th_d, (void*)c->map_best_d, (void*)c->map_sim_d, (void*)c->map_act_d,
-                    (void*)c->map_it_d})
-        if (p) (void)hipFree(p);
-    if (c->pin_th) (void)hipHostFree(c->pin_th);
-    if (c->pin_out) (void)hipHostFree(c->pin_out);
     for (hipStream_t st : c->cls_stream) (void)hipStreamDestroy(st);
     for (hipEvent_t e : c->ev_join) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (auto& p : c->ev) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
-    }
-    for (auto& p : c->xev) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
-    }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                  // (its memory and timing events with it)
     return VAMP_OK;
 }
 
@@ -3305,8 +3234,8 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
     if (n_regions > 65535) return fail(VAMP_ERR_ARG, "vamp_set_regions: at most 65535 regions per context (one grid row per region)");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_sampler(c);
-    free_regions(c);
+    reset_sampler(c);
+    reset_regions(c);
     const int q = (mode == VAMP_VOIGT4) ? 4 : 3;
     std::vector<RegionDev> R(n_regions);
     for (int r = 0; r < n_regions; ++r) {
@@ -3372,26 +3301,26 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
     const long long N = pix_off[n_regions];
     std::vector<double> wt(N);
     for (long long i = 0; i < N; ++i) wt[i] = sample_sd ? 1.0 : 1.0 / noise[i];
-    HIP_TRY(hipMalloc(&c->x_d, N * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->f_d, N * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->wt_d, N * sizeof(double)));
-    HIP_TRY(hipMemcpy(c->x_d, x, N * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->f_d, flux, N * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->wt_d, wt.data(), N * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c->x_d.ensure(N));
+    HIP_TRY(c->f_d.ensure(N));
+    HIP_TRY(c->wt_d.ensure(N));
+    HIP_TRY(hipMemcpy(c->x_d.get(), x, N * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->f_d.get(), flux, N * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->wt_d.get(), wt.data(), N * sizeof(double), hipMemcpyHostToDevice));
     if (c->f32) {
         std::vector<float> t(N);
-        HIP_TRY(hipMalloc(&c->xf_d, N * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->ff_d, N * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->wtf_d, N * sizeof(float)));
+        HIP_TRY(c->xf_d.ensure(N));
+        HIP_TRY(c->ff_d.ensure(N));
+        HIP_TRY(c->wtf_d.ensure(N));
         for (long long i = 0; i < N; ++i) t[i] = (float)x[i];
-        HIP_TRY(hipMemcpy(c->xf_d, t.data(), N * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->xf_d.get(), t.data(), N * sizeof(float), hipMemcpyHostToDevice));
         for (long long i = 0; i < N; ++i) t[i] = (float)flux[i];
-        HIP_TRY(hipMemcpy(c->ff_d, t.data(), N * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->ff_d.get(), t.data(), N * sizeof(float), hipMemcpyHostToDevice));
         for (long long i = 0; i < N; ++i) t[i] = (float)wt[i];
-        HIP_TRY(hipMemcpy(c->wtf_d, t.data(), N * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->wtf_d.get(), t.data(), N * sizeof(float), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc(&c->regions_d, n_regions * sizeof(RegionDev)));
-    HIP_TRY(hipMemcpy(c->regions_d, R.data(), n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
+    HIP_TRY(c->regions_d.ensure(n_regions));
+    HIP_TRY(hipMemcpy(c->regions_d.get(), R.data(), n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
     {
         // launch classes (csrc/host_plan.hpp, shared with the host build of this ABI).  Forced packings: one class.
         // Automatic: contexts that look like a real spectrum (<= 8 lines in every region of <= 16, mean region
@@ -3416,12 +3345,7 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
         for (int which = 0; which < 2; ++which) {
             const vamp::plan::ClassPlan& pl = which ? cs : cp;
             std::vector<LaunchClass>& part = which ? c->classes_small : c->classes;
-            for (size_t k = 0; k < pl.kind.size(); ++k) {
-                LaunchClass cl;
-                cl.kind = pl.kind[k];
-                cl.regions = pl.regions[k];
-                part.push_back(cl);
-            }
+            for (size_t k = 0; k < pl.kind.size(); ++k) part.push_back(LaunchClass{pl.kind[k], pl.regions[k]});
 #if VAMP_LPT
             // small ensembles: a launch is a few rounds of wavefronts, each a serial chain whose length grows with the region's
             // lines x pixels; the longest chains go FIRST, so that none starts in the last round (regions are independent and the
@@ -3440,8 +3364,8 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
             if (part.size() > 1)
 #endif
                 for (LaunchClass& cl : part) {
-                    HIP_TRY(hipMalloc(&cl.list_d, cl.regions.size() * sizeof(int)));
-                    HIP_TRY(hipMemcpy(cl.list_d, cl.regions.data(), cl.regions.size() * sizeof(int), hipMemcpyHostToDevice));
+                    HIP_TRY(cl.list_d.ensure(cl.regions.size()));
+                    HIP_TRY(hipMemcpy(cl.list_d.get(), cl.regions.data(), cl.regions.size() * sizeof(int), hipMemcpyHostToDevice));
                 }
         }
     }
@@ -3460,7 +3384,7 @@ int vamp_set_region_ids(vamp_ctx* c, const int32_t* ids) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int r = 0; r < c->n_regions; ++r) c->regions_h[r].rng_id = ids[r];
-    HIP_TRY(hipMemcpy(c->regions_d, c->regions_h.data(), c->n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->regions_d.get(), c->regions_h.data(), c->n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
     return VAMP_OK;
 }
 
@@ -3498,12 +3422,8 @@ int launch_lnprob(vamp_ctx* c, int region, long long W, const double* th_d, doub
         const long long per_block = shape_walkers_per_block(shape);
         const dim3 grid((unsigned)((W + per_block - 1) / per_block), all ? (unsigned)cl.regions.size() : 1u);
         const dim3 threads(shape_threads(shape));
-        if (c->f32)
-            VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_lnprob<true, M, PK>), grid, threads, 0, c->stream, c->regions_d, region,
-                                                      c->pix(), W, th_d, lp_d, ch_d, (const int*)cl.list_d));
-        else
-            VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_lnprob<false, M, PK>), grid, threads, 0, c->stream, c->regions_d, region,
-                                                      c->pix(), W, th_d, lp_d, ch_d, (const int*)cl.list_d));
+        VAMP_FOR_MODE_PK(c->f32, c->mode, shape, hipLaunchKernelGGL((k_lnprob<F32, M, PK>), grid, threads, 0, c->stream, c->regions_d.get(), region,
+                                                                c->pix(), W, th_d, lp_d, ch_d, (const int*)cl.list_d.get()));
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -3518,45 +3438,22 @@ int lnprob_impl(vamp_ctx* c, int region, int64_t W, const double* theta, double*
     const size_t nth = (size_t)W * dsum;
     const size_t nout = (size_t)W * (all ? c->n_regions : 1);
     if (nth * sizeof(double) <= PINNED_EVAL_BYTES) {
-        if (c->pin_th_cap < nth) {
-            if (c->pin_th) (void)hipHostFree(c->pin_th);
-            c->pin_th = nullptr; c->pin_th_cap = 0;
-            const size_t cap = std::max(nth, (size_t)4096);
-            HIP_TRY(hipHostMalloc(&c->pin_th, cap * sizeof(double), hipHostMallocDefault));
-            c->pin_th_cap = cap;
-        }
-        if (c->pin_out_cap < 2 * nout) {
-            if (c->pin_out) (void)hipHostFree(c->pin_out);
-            c->pin_out = nullptr; c->pin_out_cap = 0;
-            const size_t cap = std::max(2 * nout, (size_t)1024);
-            HIP_TRY(hipHostMalloc(&c->pin_out, cap * sizeof(double), hipHostMallocDefault));
-            c->pin_out_cap = cap;
-        }
-        std::memcpy(c->pin_th, theta, nth * sizeof(double));
-        double* lp_h = c->pin_out;
-        double* ch_h = chi2 ? c->pin_out + nout : nullptr;
-        int rc = launch_lnprob(c, region, W, c->pin_th, lp_h, ch_h);
+        HIP_TRY(c->pin_th.ensure(std::max(nth, (size_t)4096)));
+        HIP_TRY(c->pin_out.ensure(std::max(2 * nout, (size_t)1024)));
+        std::memcpy(c->pin_th.get(), theta, nth * sizeof(double));
+        double* lp_h = c->pin_out.get();
+        double* ch_h = chi2 ? lp_h + nout : nullptr;
+        int rc = launch_lnprob(c, region, W, c->pin_th.get(), lp_h, ch_h);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
         std::memcpy(lnprob, lp_h, nout * sizeof(double));
         if (chi2) std::memcpy(chi2, ch_h, nout * sizeof(double));
         return VAMP_OK;
     }
-    if (c->sc_th_cap < nth) {
-        if (c->sc_th) (void)hipFree(c->sc_th);
-        c->sc_th = nullptr; c->sc_th_cap = 0;
-        HIP_TRY(hipMalloc(&c->sc_th, nth * sizeof(double)));
-        c->sc_th_cap = nth;
-    }
-    if (c->sc_w_cap < nout) {
-        if (c->sc_lp) (void)hipFree(c->sc_lp);
-        if (c->sc_chi) (void)hipFree(c->sc_chi);
-        c->sc_lp = c->sc_chi = nullptr; c->sc_w_cap = 0;
-        HIP_TRY(hipMalloc(&c->sc_lp, nout * sizeof(double)));
-        HIP_TRY(hipMalloc(&c->sc_chi, nout * sizeof(double)));
-        c->sc_w_cap = nout;
-    }
-    double *th_d = c->sc_th, *lp_d = c->sc_lp, *ch_d = chi2 ? c->sc_chi : nullptr;
+    HIP_TRY(c->sc_th.ensure(nth));
+    HIP_TRY(c->sc_lp.ensure(nout));
+    HIP_TRY(c->sc_chi.ensure(nout));
+    double *th_d = c->sc_th.get(), *lp_d = c->sc_lp.get(), *ch_d = chi2 ? c->sc_chi.get() : nullptr;
     HIP_TRY(hipMemcpyAsync(th_d, theta, nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
     // (the shape must not depend on `all`: a point has the same lnprob bits through either entry)
     int rc = launch_lnprob(c, region, W, th_d, lp_d, ch_d);
@@ -3598,49 +3495,29 @@ int vamp_map_all(vamp_ctx* c, const double* theta0, const uint8_t* active, int64
         const RegionDev& last = c->regions_h.back();
         const size_t nth = (size_t)(last.d_before + last.D), nsim = (size_t)(last.sim_off + (long long)(last.D + 1) * last.D);
         const size_t nr = (size_t)c->n_regions;
-        if (c->map_th_cap < nth) {
-            for (void* p : {(void*)c->map_th_d, (void*)c->map_best_d}) if (p) (void)hipFree(p);
-            c->map_th_d = c->map_best_d = nullptr; c->map_th_cap = 0;
-            HIP_TRY(hipMalloc(&c->map_th_d, nth * sizeof(double)));
-            HIP_TRY(hipMalloc(&c->map_best_d, nth * sizeof(double)));
-            c->map_th_cap = nth;
-        }
-        if (c->map_sim_cap < nsim) {
-            if (c->map_sim_d) (void)hipFree(c->map_sim_d);
-            c->map_sim_d = nullptr; c->map_sim_cap = 0;
-            HIP_TRY(hipMalloc(&c->map_sim_d, nsim * sizeof(double)));
-            c->map_sim_cap = nsim;
-        }
-        if (c->map_r_cap < nr) {
-            if (c->map_act_d) (void)hipFree(c->map_act_d);
-            if (c->map_it_d) (void)hipFree(c->map_it_d);
-            c->map_act_d = nullptr; c->map_it_d = nullptr; c->map_r_cap = 0;
-            HIP_TRY(hipMalloc(&c->map_act_d, nr));
-            HIP_TRY(hipMalloc(&c->map_it_d, nr * sizeof(long long)));
-            c->map_r_cap = nr;
-        }
-        HIP_TRY(hipMemcpyAsync(c->map_th_d, theta0, nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (active) HIP_TRY(hipMemcpyAsync(c->map_act_d, active, nr, hipMemcpyHostToDevice, c->stream));
-        const unsigned char* act_d = active ? c->map_act_d : nullptr;
+        HIP_TRY(c->map_th_d.ensure(nth));
+        HIP_TRY(c->map_best_d.ensure(nth));
+        HIP_TRY(c->map_sim_d.ensure(nsim));
+        HIP_TRY(c->map_act_d.ensure(nr));
+        HIP_TRY(c->map_it_d.ensure(nr));
+        HIP_TRY(hipMemcpyAsync(c->map_th_d.get(), theta0, nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (active) HIP_TRY(hipMemcpyAsync(c->map_act_d.get(), active, nr, hipMemcpyHostToDevice, c->stream));
+        const unsigned char* act_d = active ? c->map_act_d.get() : nullptr;
         const std::vector<LaunchClass>& classes = partition_for(c, 1);
         for (size_t ci = 0; ci < classes.size(); ++ci) {
             const LaunchClass& cl = classes[ci];
             // the shape vamp_lnprob runs a single point of this class in: the objective has the same bits
             const int shape = class_shape(c, cl, 1, 1, true);
             const dim3 grid((unsigned)cl.regions.size()), threads(shape_threads(shape));
-            if (c->f32)
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_map_search<true, M, PK>), grid, threads, 0, c->stream, c->regions_d, c->pix(),
-                                                          (const int*)cl.list_d, c->map_th_d, act_d, (long long)maxiter, (long long)maxfun, xtol, ftol,
-                                                          c->map_sim_d, c->map_best_d, c->map_it_d));
-            else
-                VAMP_FOR_MODE_PK(c->mode, shape, hipLaunchKernelGGL((k_map_search<false, M, PK>), grid, threads, 0, c->stream, c->regions_d, c->pix(),
-                                                          (const int*)cl.list_d, c->map_th_d, act_d, (long long)maxiter, (long long)maxfun, xtol, ftol,
-                                                          c->map_sim_d, c->map_best_d, c->map_it_d));
+            VAMP_FOR_MODE_PK(c->f32, c->mode, shape, hipLaunchKernelGGL((k_map_search<F32, M, PK>), grid, threads, 0, c->stream, c->regions_d.get(),
+                                                                    c->pix(), (const int*)cl.list_d.get(), c->map_th_d.get(), act_d, (long long)maxiter,
+                                                                    (long long)maxfun, xtol, ftol, c->map_sim_d.get(), c->map_best_d.get(),
+                                                                    c->map_it_d.get()));
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipMemcpyAsync(theta_best, c->map_best_d, nth * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(theta_best, c->map_best_d.get(), nth * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         std::vector<long long> its(iterations ? nr : 0);
-        if (iterations) HIP_TRY(hipMemcpyAsync(its.data(), c->map_it_d, nr * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        if (iterations) HIP_TRY(hipMemcpyAsync(its.data(), c->map_it_d.get(), nr * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (iterations) for (size_t r = 0; r < nr; ++r) iterations[r] = its[r];
         return lnprob_impl(c, -1, 1, theta_best, lnprob_best, chi2_best);
@@ -3665,18 +3542,17 @@ int vamp_model(vamp_ctx* c, int region, const double* theta1, double* tau_comp, 
     if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_model: no such region");
     HIP_TRY(hipSetDevice(c->device));
     const RegionDev& R = c->regions_h[region];
-    DevBuf th_b, tau_b, fl_b;
-    HIP_TRY(hipMalloc(&th_b.p, R.D * sizeof(double)));
-    if (tau_comp) HIP_TRY(hipMalloc(&tau_b.p, (size_t)R.K * R.P * sizeof(double)));
-    if (flux_model) HIP_TRY(hipMalloc(&fl_b.p, (size_t)R.P * sizeof(double)));
-    double *th_d = th_b.as<double>(), *tau_d = tau_b.as<double>(), *fl_d = fl_b.as<double>();
-    HIP_TRY(hipMemcpyAsync(th_d, theta1, R.D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    DevBuf<double> th_d, tau_d, fl_d;
+    HIP_TRY(th_d.ensure(R.D));
+    if (tau_comp) HIP_TRY(tau_d.ensure((size_t)R.K * R.P));
+    if (flux_model) HIP_TRY(fl_d.ensure(R.P));
+    HIP_TRY(hipMemcpyAsync(th_d.get(), theta1, R.D * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned grid = (unsigned)((R.P + BLOCK - 1) / BLOCK);
-    VAMP_FOR_MODE(c->mode, hipLaunchKernelGGL((k_model<M>), dim3(grid), dim3(BLOCK), 0, c->stream, c->regions_d, region, c->pix(),
-                                              th_d, tau_d, fl_d));
+    VAMP_FOR_MODE(c->mode, hipLaunchKernelGGL((k_model<M>), dim3(grid), dim3(BLOCK), 0, c->stream, c->regions_d.get(), region, c->pix(),
+                                              th_d.get(), tau_d.get(), fl_d.get()));
     HIP_TRY(hipGetLastError());
-    if (tau_comp) HIP_TRY(hipMemcpyAsync(tau_comp, tau_d, (size_t)R.K * R.P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (flux_model) HIP_TRY(hipMemcpyAsync(flux_model, fl_d, (size_t)R.P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (tau_comp) HIP_TRY(hipMemcpyAsync(tau_comp, tau_d.get(), (size_t)R.K * R.P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (flux_model) HIP_TRY(hipMemcpyAsync(flux_model, fl_d.get(), (size_t)R.P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VAMP_OK;
 }
@@ -3689,17 +3565,17 @@ int vamp_model_all(vamp_ctx* c, const double* theta, double* tau_comp, double* f
     const size_t nth = (size_t)(last.d_before + last.D), ntau = (size_t)(last.tau_off + (long long)last.K * last.P);
     int pmax = 0;
     for (const RegionDev& R : c->regions_h) pmax = std::max(pmax, R.P);
-    DevBuf th_b, tau_b, fl_b;
-    HIP_TRY(hipMalloc(&th_b.p, nth * sizeof(double)));
-    if (tau_comp) HIP_TRY(hipMalloc(&tau_b.p, ntau * sizeof(double)));
-    if (flux_model) HIP_TRY(hipMalloc(&fl_b.p, (size_t)c->n_pix * sizeof(double)));
-    double *th_d = th_b.as<double>(), *tau_d = tau_b.as<double>(), *fl_d = fl_b.as<double>();
-    HIP_TRY(hipMemcpyAsync(th_d, theta, nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    DevBuf<double> th_d, tau_d, fl_d;
+    HIP_TRY(th_d.ensure(nth));
+    if (tau_comp) HIP_TRY(tau_d.ensure(ntau));
+    if (flux_model) HIP_TRY(fl_d.ensure(c->n_pix));
+    HIP_TRY(hipMemcpyAsync(th_d.get(), theta, nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const dim3 grid((unsigned)((pmax + BLOCK - 1) / BLOCK), (unsigned)c->n_regions);
-    VAMP_FOR_MODE(c->mode, hipLaunchKernelGGL((k_model<M>), grid, dim3(BLOCK), 0, c->stream, c->regions_d, -1, c->pix(), th_d, tau_d, fl_d));
+    VAMP_FOR_MODE(c->mode, hipLaunchKernelGGL((k_model<M>), grid, dim3(BLOCK), 0, c->stream, c->regions_d.get(), -1, c->pix(), th_d.get(),
+                                              tau_d.get(), fl_d.get()));
     HIP_TRY(hipGetLastError());
-    if (tau_comp) HIP_TRY(hipMemcpyAsync(tau_comp, tau_d, ntau * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (flux_model) HIP_TRY(hipMemcpyAsync(flux_model, fl_d, (size_t)c->n_pix * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (tau_comp) HIP_TRY(hipMemcpyAsync(tau_comp, tau_d.get(), ntau * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (flux_model) HIP_TRY(hipMemcpyAsync(flux_model, fl_d.get(), (size_t)c->n_pix * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VAMP_OK;
 }
@@ -3710,16 +3586,15 @@ int vamp_line_records(vamp_ctx* c, int region, const double* theta1, double* rec
     if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_line_records: no such region");
     HIP_TRY(hipSetDevice(c->device));
     const RegionDev& R = c->regions_h[region];
-    DevBuf th_b, rec_b;
-    HIP_TRY(hipMalloc(&th_b.p, R.D * sizeof(double)));
-    HIP_TRY(hipMalloc(&rec_b.p, (5 * R.K + 1) * sizeof(double)));
-    double *th_d = th_b.as<double>(), *rec_d = rec_b.as<double>();
-    HIP_TRY(hipMemcpyAsync(th_d, theta1, R.D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    VAMP_FOR_MODE(c->mode, hipLaunchKernelGGL((k_line_records<M>), dim3(1), dim3(64), 0, c->stream, c->regions_d, region, th_d,
-                                              rec_d, rec_d + 5 * R.K));
+    DevBuf<double> th_d, rec_d;
+    HIP_TRY(th_d.ensure(R.D));
+    HIP_TRY(rec_d.ensure(5 * R.K + 1));
+    HIP_TRY(hipMemcpyAsync(th_d.get(), theta1, R.D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    VAMP_FOR_MODE(c->mode, hipLaunchKernelGGL((k_line_records<M>), dim3(1), dim3(64), 0, c->stream, c->regions_d.get(), region, th_d.get(),
+                                              rec_d.get(), rec_d.get() + 5 * R.K));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rec, rec_d, 5 * R.K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(lnprior, rec_d + 5 * R.K, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(rec, rec_d.get(), 5 * R.K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(lnprior, rec_d.get() + 5 * R.K, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VAMP_OK;
 }
@@ -3727,28 +3602,25 @@ int vamp_line_records(vamp_ctx* c, int region, const double* theta1, double* rec
 int vamp_wofz_re(vamp_ctx* c, int64_t n, const double* x, const double* y, double* re_w) {
     if (!c || !x || !y || !re_w || n <= 0) return fail(VAMP_ERR_ARG, "vamp_wofz_re: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    DevBuf x_b, y_b, o_b;
-    HIP_TRY(hipMalloc(&x_b.p, n * sizeof(double)));
-    HIP_TRY(hipMalloc(&y_b.p, n * sizeof(double)));
-    HIP_TRY(hipMalloc(&o_b.p, n * sizeof(double)));
-    double *x_d = x_b.as<double>(), *y_d = y_b.as<double>(), *o_d = o_b.as<double>();
-    HIP_TRY(hipMemcpyAsync(x_d, x, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(y_d, y, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    DevBuf<double> x_d, y_d, o_d;
+    HIP_TRY(x_d.ensure(n));
+    HIP_TRY(y_d.ensure(n));
+    HIP_TRY(o_d.ensure(n));
+    HIP_TRY(hipMemcpyAsync(x_d.get(), x, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(y_d.get(), y, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    if (c->f32) hipLaunchKernelGGL((k_wofz<true>), dim3(grid), dim3(BLOCK), 0, c->stream, (long long)n, x_d, y_d, o_d);
-    else hipLaunchKernelGGL((k_wofz<false>), dim3(grid), dim3(BLOCK), 0, c->stream, (long long)n, x_d, y_d, o_d);
+    VAMP_FOR_F32(c->f32, hipLaunchKernelGGL((k_wofz<F32>), dim3(grid), dim3(BLOCK), 0, c->stream, (long long)n, x_d.get(), y_d.get(), o_d.get()));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(re_w, o_d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(re_w, o_d.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VAMP_OK;
 }
 
 int vamp_sampler_bind_state(vamp_ctx* c, void* X_dev, void* lnp_dev) {
     if (!c || !X_dev || !lnp_dev) return fail(VAMP_ERR_ARG, "vamp_sampler_bind_state: NULL argument");
-    free_sampler(c);
+    reset_sampler(c);
     c->X_d = (double*)X_dev;
     c->lnp_d = (double*)lnp_dev;
-    c->X_ext = true;
     return VAMP_OK;
 }
 
@@ -3767,10 +3639,10 @@ int vamp_sampler_init(vamp_ctx* c, int64_t W, const double* theta0, uint64_t see
         c->regions_h[r].walker_off = (long long)r * W;
         tt += (long long)W * c->regions_h[r].D;
     }
-    HIP_TRY(hipMemcpy(c->regions_d, c->regions_h.data(), c->n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
-    const bool ext = c->X_ext && c->X_d;
-    if (!ext) free_sampler(c);
-    if (c->nacc_d) { (void)hipFree(c->nacc_d); c->nacc_d = nullptr; }
+    HIP_TRY(hipMemcpy(c->regions_d.get(), c->regions_h.data(), c->n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
+    const bool bound = c->X_d && c->X_d != c->X_own.get();      // the caller's state (vamp_sampler_bind_state) is kept
+    if (!bound) reset_sampler(c);
+    c->nacc_d.reset();
     c->W = W;
     c->total_theta = tt;
     c->total_walkers = (long long)c->n_regions * W;
@@ -3778,13 +3650,14 @@ int vamp_sampler_init(vamp_ctx* c, int64_t W, const double* theta0, uint64_t see
     c->a = a;
     c->seed = seed;
     c->step = 0;
-    if (!ext) {
-        c->X_ext = false;
-        HIP_TRY(hipMalloc(&c->X_d, tt * sizeof(double)));
-        HIP_TRY(hipMalloc(&c->lnp_d, c->total_walkers * sizeof(double)));
+    if (!bound) {
+        HIP_TRY(c->X_own.ensure(tt));
+        HIP_TRY(c->lnp_own.ensure(c->total_walkers));
+        c->X_d = c->X_own.get();
+        c->lnp_d = c->lnp_own.get();
     }
-    HIP_TRY(hipMalloc(&c->nacc_d, c->total_walkers * sizeof(long long)));
-    HIP_TRY(hipMemsetAsync(c->nacc_d, 0, c->total_walkers * sizeof(long long), c->stream));
+    HIP_TRY(c->nacc_d.ensure(c->total_walkers));
+    HIP_TRY(hipMemsetAsync(c->nacc_d.get(), 0, c->total_walkers * sizeof(long long), c->stream));
     HIP_TRY(hipMemcpyAsync(c->X_d, theta0, tt * sizeof(double), hipMemcpyHostToDevice, c->stream));
     // initial log-posteriors of every walker: the state has the layout of vamp_lnprob_all's arguments
     // (block r at W * d_before(r), lnprob of region r at r * W), so this is one launch per launch class
@@ -3827,9 +3700,8 @@ int vamp_sampler_set_shard_parts(vamp_ctx* c, int rank, int world, int parts, in
     // exchange buffers: the movers of every part in slot order, position + lnprob per row
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->send_d) (void)hipFree(c->send_d);
-    if (c->recv_d) (void)hipFree(c->recv_d);
-    c->send_d = c->recv_d = nullptr;
+    c->send_d.reset();
+    c->recv_d.reset();
     if (world > 1 || c->comm) {
         int rc = alloc_exchange_buffers(c);
         if (rc) return rc;
@@ -3898,20 +3770,14 @@ int vamp_sampler_half_step_ext(vamp_ctx* c, int region, int64_t n, const int32_t
     for (int64_t i = 0; i < n; ++i)
         if (is_active[partner_idx[i]]) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: partner must belong to the frozen complement");
     HIP_TRY(hipSetDevice(c->device));
-    if (c->ext_cap < n) {
-        for (void* p : {(void*)c->ext_act_d, (void*)c->ext_par_d, (void*)c->ext_z_d, (void*)c->ext_lu_d})
-            if (p) (void)hipFree(p);
-        c->ext_cap = 0;
-        HIP_TRY(hipMalloc(&c->ext_act_d, n * sizeof(int)));
-        HIP_TRY(hipMalloc(&c->ext_par_d, n * sizeof(int)));
-        HIP_TRY(hipMalloc(&c->ext_z_d, n * sizeof(double)));
-        HIP_TRY(hipMalloc(&c->ext_lu_d, n * sizeof(double)));
-        c->ext_cap = n;
-    }
-    HIP_TRY(hipMemcpyAsync(c->ext_act_d, active_idx, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ext_par_d, partner_idx, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ext_z_d, zz, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ext_lu_d, logu, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->ext_act_d.ensure(n));
+    HIP_TRY(c->ext_par_d.ensure(n));
+    HIP_TRY(c->ext_z_d.ensure(n));
+    HIP_TRY(c->ext_lu_d.ensure(n));
+    HIP_TRY(hipMemcpyAsync(c->ext_act_d.get(), active_idx, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ext_par_d.get(), partner_idx, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ext_z_d.get(), zz, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ext_lu_d.get(), logu, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     int rc = launch_half(c, 0, true, region, n);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3969,19 +3835,14 @@ int vamp_sampler_run(vamp_ctx* c, int64_t n_steps, int thin, double* chain, doub
     if (n_steps < 0 || thin < 1) return fail(VAMP_ERR_ARG, "vamp_sampler_run: n_steps >= 0 and thin >= 1 required");
     HIP_TRY(hipSetDevice(c->device));
     const long long n_keep = n_steps / thin;
-    DevBuf chain_b, lchain_b;
-    if (chain && n_keep) HIP_TRY(hipMalloc(&chain_b.p, (size_t)n_keep * c->total_theta * sizeof(double)));
-    if (lnprob_chain && n_keep) HIP_TRY(hipMalloc(&lchain_b.p, (size_t)n_keep * c->total_walkers * sizeof(double)));
-    double *chain_d = chain_b.as<double>(), *lchain_d = lchain_b.as<double>();
-    int rc = vamp_sampler_run_dev(c, n_steps, thin, chain_d, lchain_d, seconds);
+    DevBuf<double> chain_d, lchain_d;
+    if (chain && n_keep) HIP_TRY(chain_d.ensure((size_t)n_keep * c->total_theta));
+    if (lnprob_chain && n_keep) HIP_TRY(lchain_d.ensure((size_t)n_keep * c->total_walkers));
+    int rc = vamp_sampler_run_dev(c, n_steps, thin, chain_d.get(), lchain_d.get(), seconds);
     if (rc) return rc;
-    if (chain_d) {
-        HIP_TRY(hipMemcpy(chain, chain_d, (size_t)n_keep * c->total_theta * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (lchain_d) {
-        HIP_TRY(hipMemcpy(lnprob_chain, lchain_d, (size_t)n_keep * c->total_walkers * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (n_accept) HIP_TRY(hipMemcpy(n_accept, c->nacc_d, c->total_walkers * sizeof(long long), hipMemcpyDeviceToHost));
+    if (chain_d) HIP_TRY(hipMemcpy(chain, chain_d.get(), (size_t)n_keep * c->total_theta * sizeof(double), hipMemcpyDeviceToHost));
+    if (lchain_d) HIP_TRY(hipMemcpy(lnprob_chain, lchain_d.get(), (size_t)n_keep * c->total_walkers * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_accept) HIP_TRY(hipMemcpy(n_accept, c->nacc_d.get(), c->total_walkers * sizeof(long long), hipMemcpyDeviceToHost));
     return VAMP_OK;
 }
 
@@ -4072,7 +3933,7 @@ int vamp_sampler_pack_get(vamp_ctx* c, int part, double* rows) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->part_slots * (c->regions_h[0].D + 1);
-    HIP_TRY(hipMemcpy(rows, c->send_d + (size_t)part * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rows, c->send_d.get() + (size_t)part * n, n * sizeof(double), hipMemcpyDeviceToHost));
     return VAMP_OK;
 }
 
@@ -4082,7 +3943,7 @@ int vamp_sampler_scatter_put(vamp_ctx* c, int part, const double* rows_all) {
     if (part < 0 || part >= c->shard_parts) return fail(VAMP_ERR_ARG, "vamp_sampler_scatter_put: no such part");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->shard_world * c->part_slots * (c->regions_h[0].D + 1);
-    HIP_TRY(hipMemcpyAsync(c->recv_d + (size_t)part * n, rows_all, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->recv_d.get() + (size_t)part * n, rows_all, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     int rc = launch_scatter(c, part, c->stream);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4096,7 +3957,7 @@ int vamp_sampler_get_state(vamp_ctx* c, double* theta, double* lnprob, int64_t* 
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (theta) HIP_TRY(hipMemcpy(theta, c->X_d, c->total_theta * sizeof(double), hipMemcpyDeviceToHost));
     if (lnprob) HIP_TRY(hipMemcpy(lnprob, c->lnp_d, c->total_walkers * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_accept) HIP_TRY(hipMemcpy(n_accept, c->nacc_d, c->total_walkers * sizeof(long long), hipMemcpyDeviceToHost));
+    if (n_accept) HIP_TRY(hipMemcpy(n_accept, c->nacc_d.get(), c->total_walkers * sizeof(long long), hipMemcpyDeviceToHost));
     if (step) *step = c->step;
     return VAMP_OK;
 }
@@ -4116,12 +3977,12 @@ int vamp_sampler_set_state(vamp_ctx* c, const double* theta, const double* lnpro
 int vamp_exchange_timing(vamp_ctx* c, double* total_ms, int64_t* exchanges) {
     if (!c) return fail(VAMP_ERR_ARG, "vamp_exchange_timing: ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = flush_exchange_timing(c);
+    int rc = c->xtiming.flush();
     if (rc) return rc;
-    if (total_ms) *total_ms = c->xtiming_ms;
-    if (exchanges) *exchanges = c->xtiming_n;
-    c->xtiming_ms = 0.0;
-    c->xtiming_n = 0;
+    if (total_ms) *total_ms = c->xtiming.ms;
+    if (exchanges) *exchanges = c->xtiming.n;
+    c->xtiming.ms = 0.0;
+    c->xtiming.n = 0;
     return VAMP_OK;
 }
 
@@ -4141,14 +4002,14 @@ int vamp_debug_stamps(unsigned long long* out, int cap) {
 int vamp_kernel_timing(vamp_ctx* c, int enable, double* total_ms, int64_t* launches) {
     if (!c) return fail(VAMP_ERR_ARG, "vamp_kernel_timing: ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = flush_timing(c);
+    int rc = c->ktiming.flush();
     if (rc) return rc;
-    rc = flush_exchange_timing(c);
+    rc = c->xtiming.flush();
     if (rc) return rc;
-    if (total_ms) *total_ms = c->timing_ms;
-    if (launches) *launches = c->timing_launches;
-    c->timing_ms = 0.0;
-    c->timing_launches = 0;
+    if (total_ms) *total_ms = c->ktiming.ms;
+    if (launches) *launches = c->ktiming.n;
+    c->ktiming.ms = 0.0;
+    c->ktiming.n = 0;
     c->timing = enable != 0;
     return VAMP_OK;
 }
