@@ -2,7 +2,12 @@
 """Headline benchmark: walker-steps/s of the stretch-move + Voigt log-posterior hot path on the
 synthetic 16 384-pixel x 16-component x 65 536-walker region of BASELINE.json (config 4).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing more: it synthesises the workload, warms up, times the K
+steps, writes --dump-outputs if asked and prints the line.  `--full` adds what takes time of its own: the CPU
+baselines (fp64, one rank; `cpu_baseline`) before the GPU is touched, and after the timed steps a sustained second
+run of --sustain-seconds (`sustained`).  Both leave the timed steps, their inputs and what they compute alone.
 
 N > 1: one rank per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 every rank finds RANK / LOCAL_RANK / WORLD_SIZE in its environment.  Started plainly (`python bench.py
@@ -383,11 +388,13 @@ def main():
                     help="initial walkers: the truth ball of SURVEY 8d (default, the headline); 'dispersed' = a burn-in "
                          "ensemble (own centroids, amplitudes and log-uniform widths per walker); 'prior' = drawn from the priors")
     ap.add_argument("--width-scale", type=float, default=1.0, help="multiply the true line widths (G and L) of the workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure the CPU baselines and a sustained second run (see --sustain-seconds)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-chain", action="store_true", help="do not record the chain inside the timed region")
-    ap.add_argument("--sustain-seconds", type=float, default=10.0,
-                    help="after the K timed steps, a second run of about this many seconds (0 = skip); long enough for a "
-                         "driver that samples GPU activity every few seconds to land inside the kernel")
+    ap.add_argument("--sustain-seconds", type=float, default=None,
+                    help="with --full: after the K timed steps, a second run of about this many seconds (default 10, 0 = skip); "
+                         "long enough for a driver that samples GPU activity every few seconds to land inside the kernel")
     ap.add_argument("--force-dist", action="store_true",
                     help="create the RCCL communicator and run the exchange even with one rank (rehearsal)")
     ap.add_argument("--exchange-parts", default="auto",
@@ -399,6 +406,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.sustain_seconds is None:
+        args.sustain_seconds = 10.0 if args.full else 0.0
+    elif args.sustain_seconds > 0 and not args.full:
+        ap.error("a sustained run (--sustain-seconds > 0) is part of --full")
 
     # the host driver of these boxes only supports dmabuf IPC: without this RCCL's intra-node handles fail
     # (hipIpcGetMemHandle: invalid argument).  Already exported on the boxes; kept for any other launcher.
@@ -418,7 +429,7 @@ def main():
 
     # host baseline first: its worker pool forks before this process has touched the GPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.dtype == "f64":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.dtype == "f64":
         cpu = cpu_baseline(wl)
 
     import torch

@@ -519,9 +519,9 @@ def test_pieces_of_a_packed_single_region_ensemble():
 
 # ---- round 3: bench.py as the driver runs it, fall-back safety net, call order, shape under sharding ----
 FAKE_RCCL = os.path.join(ROOT, "tests", "host", "librccl_fake.so")
-# (a short second run too: its length is derived from the timed run, and every rank must derive the same one)
-BENCH_SMALL = ["--walkers", "4096", "--pixels", "2048", "--components", "6", "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--sustain-seconds", "0.2"]
+BENCH_PLAIN = ["--walkers", "4096", "--pixels", "2048", "--components", "6", "--steps", "2", "--warmup", "1"]
+# --full: a short second run too (its length is derived from the timed run, and every rank must derive the same one)
+BENCH_SMALL = BENCH_PLAIN + ["--full", "--no-cpu-baseline", "--sustain-seconds", "0.2"]
 
 
 def _run_bench(extra_args, extra_env, timeout=600):
@@ -582,6 +582,28 @@ def test_bench_driver_form_is_not_a_rehearsal():
     ex = line["exchange"]
     assert line["rehearsal"] is False and line["rccl_ranks"] == 1 and ex["kind"] == "rccl"
     assert "librccl" in os.path.basename(ex["rccl_library"]) and ex["distinct_devices"] == 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full the benchmark warms up, times its steps, dumps what they computed and prints the headline line:
+    no CPU baselines, no sustained second run."""
+    line, _ = _run_bench(BENCH_PLAIN + ["--dump-outputs", str(tmp_path)], {})
+    assert "cpu_baseline" not in line and "sustained" not in line
+    assert line["metric"] == "walker-steps/sec (log-posterior evals/sec)" and line["unit"] == "walker-steps/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and line["value"] * line["ms_per_step"] == pytest.approx(4096 * 1e3)
+    assert line["finite_lnprob_fraction"] == 1.0
+    assert line["dump_outputs"]["files"] == ["chain_last.npy", "lnprob.npy", "n_accept.npy", "theta.npy"]
+    assert np.load(tmp_path / "theta.npy").shape == (4096, 18) and np.load(tmp_path / "lnprob.npy").shape == (4096,)
+
+
+def test_bench_sustained_run_needs_full():
+    """The sustained second run belongs to --full: asking for one without it is a usage error, before any GPU work."""
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sustain-seconds", "1"], capture_output=True,
+                         text=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 2 and "--full" in out.stderr and not out.stdout
 
 
 @pytest.mark.gpu

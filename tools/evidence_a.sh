@@ -4,10 +4,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 cd $R
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
-python3 bench.py --dtype f32 --no-cpu-baseline --sustain-seconds 2.5 > $OUT/headline_f32_bench.json 2>> $OUT/bench.err
-python3 bench.py --force-dist --no-cpu-baseline --sustain-seconds 2.5 > $OUT/bench_rccl_rehearsal_world1.json 2>> $OUT/bench.err
+python3 bench.py --full --dtype f32 --no-cpu-baseline --sustain-seconds 2.5 > $OUT/headline_f32_bench.json 2>> $OUT/bench.err
+python3 bench.py --full --force-dist --no-cpu-baseline --sustain-seconds 2.5 > $OUT/bench_rccl_rehearsal_world1.json 2>> $OUT/bench.err
 python3 tools/bench_c3.py --steps 20 > $OUT/c3_bench.json
 python3 tools/bench_c3.py --steps 20 --dtype f32 > $OUT/c5_q1422_f32_bench.json
 echo "benches done"

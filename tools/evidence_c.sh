@@ -19,6 +19,6 @@ echo "gpu suite done: $(tail -1 $OUT/gputests.log)"
 echo "soaks done"
 python tools/robustness.py --steps 10 > $OUT/robustness.txt 2>&1
 echo "robustness done"
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --dtype f32 --no-cpu-baseline > $OUT/bench_f32.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --dtype f32 --no-cpu-baseline > $OUT/bench_f32.json 2>> $OUT/bench.err
 tail -c 600 $OUT/bench.json
