@@ -107,6 +107,50 @@ def test_error_codes_and_call_order(cpu_lib, cpu_ctx):
     assert out[0] == -np.inf and out[1] == -np.inf and np.isfinite(out[2:]).all()
 
 
+def test_host_rules_shared_with_the_product(cpu_lib, cpu_ctx):
+    """The ABI rules csrc/abi_state.hpp states once for both libraries: a region index is range-checked by every entry
+    point that takes one, the region limit of a launch, vamp_sampler_run's own checks, a communicator that must agree
+    with the shard already set (and whose exchange then belongs to half_step / run), and a re-initialised sampler that
+    has no exchange buffers."""
+    import vamp_amd
+    E = vamp_amd._lib.VampError
+    dp = lambda a: a.ctypes.data_as(vamp_amd._lib.c_double_p)
+    g = load_golden("stretch_traj.npz")
+    cpu_ctx.set_regions(g["x"], g["flux"], g["noise"], 1, mode=vo.MODE_VOIGT4)
+    th, rec, lnprior, out = g["X0"][0].copy(), np.zeros(5), np.zeros(1), np.zeros(g["x"].size)
+    for region in (-1, -2, 1):
+        assert cpu_lib.vamp_model(cpu_ctx._h, region, dp(th), None, dp(out)) == -1
+        assert cpu_lib.vamp_last_error() == b"vamp_model: no such region"
+        assert cpu_lib.vamp_line_records(cpu_ctx._h, region, dp(th), dp(rec), dp(lnprior)) == -1
+        assert cpu_lib.vamp_last_error() == b"vamp_line_records: no such region"
+    n = 65536
+    pix_off = np.arange(0, 2 * n + 1, 2, dtype=np.int64)
+    xs, ones, k = np.tile([0.0, 1.0], n), np.ones(2 * n), np.ones(n, dtype=np.int32)
+    assert cpu_lib.vamp_set_regions(cpu_ctx._h, n, pix_off.ctypes.data_as(vamp_amd._lib.c_int64_p), dp(xs), dp(ones), dp(ones),
+                                    k.ctypes.data_as(vamp_amd._lib.c_int32_p), vo.MODE_VOIGT4, 0, 0, None, None) == -1
+    assert b"at most 65535 regions" in cpu_lib.vamp_last_error()
+    cpu_ctx.set_regions(g["x"], g["flux"], g["noise"], 1, mode=vo.MODE_VOIGT4)
+    assert cpu_lib.vamp_sampler_run(cpu_ctx._h, 1, 1, None, None, None, None) == -5
+    assert cpu_lib.vamp_last_error() == b"vamp_sampler_run: call vamp_sampler_init first"
+    cpu_ctx.sampler_init(g["X0"], seed=1, split_block=8)
+    assert cpu_lib.vamp_sampler_run(cpu_ctx._h, -1, 1, None, None, None, None) == -1
+    assert cpu_lib.vamp_last_error().startswith(b"vamp_sampler_run: ")
+    cpu_ctx.sampler_set_shard_parts(1, 2, 1)
+    cpu_ctx.pack_get(0)                                       # world 2: exchange buffers
+    with pytest.raises(E) as e:                               # the communicator disagrees with the shard
+        cpu_ctx.comm_init_rank(b"vamp-cpu" + bytes(120), 0, 1)
+    assert e.value.code == -1 and b"differ from the shard" in cpu_lib.vamp_last_error()
+    cpu_ctx.sampler_init(g["X0"], seed=1, split_block=8)      # a new ensemble has no exchange buffers
+    with pytest.raises(E) as e:
+        cpu_ctx.pack_get(0)
+    assert e.value.code == -5
+    cpu_ctx.sampler_set_shard_parts(0, 1, 1)
+    cpu_ctx.comm_init_rank(b"vamp-cpu" + bytes(120), 0, 1)    # the shard came first: its exchange is due now ...
+    with pytest.raises(E) as e:                               # ... and part of half_step / run
+        cpu_ctx.half_step_part(0, 0)
+    assert e.value.code == -5
+
+
 def test_pack_and_scatter_arithmetic(cpu_ctx):
     """The active-colour exchange of a 2-shard context (vamp_sampler_pack_get / scatter_put): same
     assertions as the GPU test of the scatter kernel."""

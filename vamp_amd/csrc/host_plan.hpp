@@ -3,7 +3,9 @@
 // workgroups a packed launch takes, which contexts the device-resident step loop takes.  No HIP in here: the
 // same header is compiled into oracle/libvamp_cpu.so (the host implementation of the C ABI), whose
 // AddressSanitizer + UndefinedBehaviorSanitizer build runs it under tests/test_sanitizers.py -- GPU sanitizers
-// are not available on this pool, this is how the product's own host code gets sanitizer coverage.
+// are not available, this is how the product's own host code gets sanitizer coverage.  The rest of the ABI's host
+// rules (checks, region table, sampler and shard bookkeeping) are shared the same way through abi_state.hpp, the
+// sampler's draws through draws.hpp.
 //
 // Reference: none of this exists there (one process, one region at a time: vpspectrum.py:273-348); the regions'
 // sizes it plans for are the reference's (vpspectrum.py:287-294: more than 15 / 22.5 lines are "difficult").
@@ -49,6 +51,11 @@ struct ClassPlan {
     bool spectrum_like = false;
 };
 
+// Forced packings: one class.  Automatic: contexts that look like a real spectrum (<= 8 lines in every region of <= 16,
+// mean region <= 128 px) split into the blends worth a wavefront and a set of Taylor tables per walker (>= 3 lines over
+// 96 .. 512 px: table building costs ~2 near-axis evaluations per line and interval, repaid from ~30 px per line on),
+// the one- and two-line regions (eight walkers per wavefront) and the rest (four); regions of more than 16 lines form
+// their own class (plain shape PackXL); everything else is one wide class.
 // packing: 0 automatic, 16 / 64 / 65 / 256 forced (vamp_ctx_set_packing).  gauss: Gaussian components (no tables).
 // tables_f32: fp32 contexts have single-precision Taylor rows for their blends.  Returns "" or an error message.
 // merged: the partition for SMALL ENSEMBLES (<= 128 movers per region: model-selection ladders, single points, the MAP

@@ -43,6 +43,8 @@
 #include <vector>
 
 #include "../../include/vamp_hip.h"
+#include "abi_state.hpp"
+#include "draws.hpp"
 #include "host_plan.hpp"
 #include "map_search.hpp"
 #include "voigt_math.hpp"
@@ -137,25 +139,7 @@ constexpr double SQRT_PI = 1.77245385090551602730;
 constexpr double FWHM_PER_SIGMA = 2.35482004503094938202;   // 2 sqrt(2 ln 2), vpfits.py:88,326
 constexpr double NEG_INF = -__builtin_huge_val();
 
-// ---------------------------------------------------------------------------------------
-// device-side description of one region (one posterior)
-// ---------------------------------------------------------------------------------------
-struct RegionDev {
-    long long pix_off;     // into x / flux / wt
-    long long theta_off;   // doubles: start of this region's [W, D] block in the sampler state
-    long long walker_off;  // first global walker id of this region in the sampler state
-    long long d_before;    // sum of D over the preceding regions (vamp_lnprob_all: block r starts at W * d_before)
-    long long tau_off;     // sum of K * P over the preceding regions (vamp_model_all: this region's tau_comp block)
-    long long sim_off;     // sum of (D + 1) * D over the preceding regions (k_map_search: this region's simplex)
-    int P, K, mode, D;     // D = q*K (+1 if sample_sd)
-    int sample_sd, q, rng_id, pad1;   // rng_id: the region's identity in the draw keys (default: its index)
-    double c_lo, c_hi;     // centroid prior (vpfits.py:250,293)
-    double w_max;          // sigma_max (GAUSS3, vpfits.py:320) or fwhm_max (vpfits.py:326)
-    double lp_c, lp_w;     // -log(c_hi - c_lo), -log(w_max): uniform log-densities
-    double l_fixed, line, x_origin, x_scale;   // NBZ3
-    double norm_const;     // -1/2 sum log(2 pi sigma^2) or 0
-    double tile_span;      // 64 * TPIX * (largest pixel spacing of the region)
-};
+using vamp::RegionDev;        // one region (one posterior): abi_state.hpp
 
 struct LineRec {           // per (walker, component), lives in LDS
     double c;              // centroid
@@ -1956,48 +1940,8 @@ __global__ __launch_bounds__(BLOCK) void k_wofz(long long n, const double* __res
     }
 }
 
-// ---- counter-based RNG: Philox4x32-10 (Salmon et al., SC'11) ------------------------------
-struct U4 { unsigned c0, c1, c2, c3; };
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c.c0;
-        const unsigned long long p1 = 0xCD9E8D57ull * c.c2;
-        U4 n;
-        n.c0 = (unsigned)(p1 >> 32) ^ c.c1 ^ k0;
-        n.c1 = (unsigned)p1;
-        n.c2 = (unsigned)(p0 >> 32) ^ c.c3 ^ k1;
-        n.c3 = (unsigned)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-__device__ __forceinline__ double u53(unsigned hi, unsigned lo) {
-    return (double)((((unsigned long long)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-}
-constexpr unsigned STREAM_MOVE = 0, STREAM_ACCEPT = 1, STREAM_SPLIT = 2;
-
-// keyed bijection of [0, block): affine-multiply / xorshift rounds on the next power of two,
-// cycle-walking back into range (DESIGN.md "red/blue split")
-__device__ __forceinline__ unsigned split_perm(unsigned long long seed, unsigned step, unsigned chunk, unsigned region,
-                                               unsigned slot, unsigned block) {
-    const U4 r = philox4x32_10({chunk, step, STREAM_SPLIT, region}, (unsigned)seed, (unsigned)(seed >> 32));
-    int bits = 32 - __builtin_clz((block - 1) | 1u);
-    if (bits < 1) bits = 1;
-    const unsigned long long mask = (1ull << bits) - 1ull;
-    int sh = bits / 2;
-    if (sh < 1) sh = 1;
-    const unsigned long long m0 = ((unsigned long long)r.c0 << 1) | 1ull, m2 = ((unsigned long long)r.c2 << 1) | 1ull;
-    unsigned long long v = slot;
-    for (;;) {
-        v = (v * m0 + r.c1) & mask;  v ^= v >> sh;
-        v = (v * m2 + r.c3) & mask;  v ^= v >> sh;
-        v = (v * 0x9E3779B1ull + (r.c0 ^ r.c3)) & mask;  v ^= v >> sh;
-        if (v < block) return (unsigned)v;
-    }
-}
+// ---- counter-based draws: Philox4x32-10, the keyed red/blue split, the draws of a mover (draws.hpp) ----
+using vamp::MoveDraw; using vamp::draw_move;
 
 struct SamplerDev {
     const RegionDev* regions;
@@ -2020,36 +1964,7 @@ struct SamplerDev {
                                  // groups); 0: slots are dealt to wavefronts linearly (one region, or one walker per wavefront)
 };
 
-// The draws of one mover: which walker holds active slot `a_loc` of `region` in this (step, half),
-// its stretch factor, its partner from the frozen colour and log(u2) for the accept test.
-struct MoveDraw { long long ws, wc; double z, logu; };
-__device__ __forceinline__ MoveDraw draw_move(const SamplerDev& S, unsigned step, int half, int region, long long a_loc) {
-    const long long halfW = S.W >> 1;
-    const unsigned hb = (unsigned)(S.split_block >> 1);
-    const unsigned chunk = (unsigned)(a_loc / hb);
-    const unsigned pos = (unsigned)(a_loc % hb);
-    MoveDraw d;
-    // draws are keyed by the region's rng_id, not by its position in this context: a region follows
-    // the same trajectory whichever device (and whichever subset of a spectrum's regions) holds it
-    const unsigned rid = (unsigned)S.regions[region].rng_id;
-    d.ws = (long long)chunk * S.split_block +
-           split_perm(S.seed, step, chunk, rid, pos + (half ? hb : 0u), (unsigned)S.split_block);
-    const long long gid = (long long)rid * S.W + d.ws;
-    const unsigned k0 = (unsigned)S.seed, k1 = (unsigned)(S.seed >> 32);
-    const U4 r = philox4x32_10({(unsigned)gid, step, ((unsigned)half << 8) | STREAM_MOVE, (unsigned)(gid >> 32)}, k0, k1);
-    const double u1 = u53(r.c0, r.c1);
-    const double t = (S.a - 1.0) * u1 + 1.0;
-    d.z = t * t / S.a;
-    const unsigned long long j = __umul64hi(((unsigned long long)r.c2 << 32) | r.c3, (unsigned long long)halfW);
-    const unsigned cchunk = (unsigned)(j / hb);
-    const unsigned cpos = (unsigned)(j % hb);
-    d.wc = (long long)cchunk * S.split_block +
-           split_perm(S.seed, step, cchunk, rid, cpos + (half ? 0u : hb), (unsigned)S.split_block);
-    const U4 r2 = philox4x32_10({(unsigned)gid, step, ((unsigned)half << 8) | STREAM_ACCEPT, (unsigned)(gid >> 32)}, k0, k1);
-    const double u2 = u53(r2.c0, r2.c1);
-    d.logu = u2 > 0.0 ? log(u2) : NEG_INF;
-    return d;
-}
+__host__ __device__ __forceinline__ int region_rng_id(const SamplerDev& S, int region) { return S.regions[region].rng_id; }
 
 // Draws of a whole launch, one THREAD per mover.  A wavefront that serves one walker computes its
 // draws on the scalar unit for free; packed four to a wavefront the same integer arithmetic runs
@@ -2342,7 +2257,7 @@ __global__ __launch_bounds__(256) void k_scatter_rows(SamplerDev S, const double
     const unsigned hb = (unsigned)(S.split_block >> 1);
     const unsigned chunk = (unsigned)(slot / hb), pos = (unsigned)(slot % hb);
     const long long ws = (long long)chunk * S.split_block +
-                         split_perm(S.seed, step, chunk, (unsigned)R.rng_id, pos + (half ? hb : 0u), (unsigned)S.split_block);
+                         vamp::split_perm(S.seed, step, chunk, (unsigned)R.rng_id, pos + (half ? hb : 0u), (unsigned)S.split_block);
     const double* src = recv + i * (long long)(D + 1);
     double* dst = S.X + R.theta_off + ws * D;
     for (int d = l; d < D; d += 16) dst[d] = src[d];
@@ -2352,12 +2267,7 @@ __global__ __launch_bounds__(256) void k_scatter_rows(SamplerDev S, const double
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
+using vamp::fail;
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
@@ -2497,25 +2407,16 @@ struct EventPairs {
 
 }  // namespace
 
-struct vamp_ctx {
+// the state the host implementation of the ABI shares (vamp::AbiState: regions, class plan, sampler scalars, shard and
+// part bookkeeping, communicator) and what lives on the device
+struct vamp_ctx : vamp::AbiState {
     int device = 0;
-    int dtype = VAMP_F64;
     int wofz_kind = VAMP_WOFZ_ACCURATE;
-    bool f32 = false;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
-    // regions
-    int n_regions = 0;
-    int mode = VAMP_VOIGT4;
-    int packing = 0;       // requested: 0 = auto, 16 or 64 lanes per walker, 256 = a 4-wave workgroup per walker
-    int min_tiles = 0;     // full 256-pixel tiles of the shortest region
-    bool full_tiles = false;   // every region's pixel count is a multiple of 64 * TPIX
-    std::vector<LaunchClass> classes;      // partition of the regions by kernel shape (vamp_set_regions)
-    std::vector<int> class_of;             // region -> index into classes
-    // the partition for SMALL ensembles (<= RES_MAX_MOVERS movers per region): the short-region classes merged into one
-    // (vamp::plan::plan_classes, merged) -- a class is a launch per half-step, and there launches are what a half-step costs
+    // the launch classes of plan and plan_small (vamp_set_regions): one launch per class and half-step
+    std::vector<LaunchClass> classes;
     std::vector<LaunchClass> classes_small;
-    std::vector<int> class_of_small;
     // draws of packed launches (k_draws), grown on demand
     DevBuf<int> dr_ws, dr_wc;
     DevBuf<double> dr_z, dr_lu, dr_lz;
@@ -2526,34 +2427,20 @@ struct vamp_ctx {
     std::vector<hipStream_t> cls_stream;
     hipEvent_t ev_fork = nullptr;
     std::vector<hipEvent_t> ev_join;
-    std::vector<RegionDev> regions_h;
     DevBuf<RegionDev> regions_d;
     long long n_pix = 0;
     DevBuf<double> x_d, f_d, wt_d;
     DevBuf<float> xf_d, ff_d, wtf_d;
-    // sampler
-    bool sampler_ready = false;
-    long long W = 0, total_theta = 0, total_walkers = 0;
-    int split_block = 0;
-    double a = 2.0;
-    unsigned long long seed = 0;
-    long long step = 0;
     // the state: X_d / lnp_d are the walkers' positions and lnprobs, in X_own / lnp_own or in the caller's memory
     // (vamp_sampler_bind_state)
     double* X_d = nullptr;
     double* lnp_d = nullptr;
     DevBuf<double> X_own, lnp_own;
     DevBuf<long long> nacc_d;
-    long long slot_begin = 0, slot_end = 0;      // part 0 (the whole share when shard_parts == 1)
-    int shard_rank = 0, shard_world = 1, shard_parts = 1;
-    long long part_slots = 0, part_stride = 0;   // slots per part; distance between this rank's parts
-    // walker-sharded runs: active-colour exchange (pack -> all-gather -> scatter), see vamp_comm_*
+    // walker-sharded runs: the exchange buffers (AbiState::exchange), see vamp_comm_*
     DevBuf<double> send_d;           // [parts][part_slots][D + 1]
     DevBuf<double> recv_d;           // [parts][world * part_slots][D + 1]
-    std::vector<unsigned> part_step; // (step, half) of the last launch of every part
-    std::vector<int> part_half;
-    void* comm = nullptr;            // ncclComm_t (RCCL), one per ctx
-    int comm_rank = 0, comm_world = 1;
+    void* rccl = nullptr;            // ncclComm_t (RCCL), one per ctx
     hipStream_t comm_stream = nullptr;
     std::vector<hipEvent_t> ev_kernel, ev_scatter;   // per part: kernel done / rows scattered
     // exchange timing (vamp_exchange_timing): event pairs around all-gather + scatter on the stream they run on
@@ -2590,10 +2477,7 @@ void reset_regions(vamp_ctx* c) {
     c->xf_d.reset(); c->ff_d.reset(); c->wtf_d.reset();
     c->classes.clear();
     c->classes_small.clear();
-    c->class_of.clear();
-    c->class_of_small.clear();
     c->n_regions = 0;
-    c->regions_h.clear();
 }
 
 // forgets the state, also a bound one (vamp_sampler_bind_state)
@@ -2602,6 +2486,7 @@ void reset_sampler(vamp_ctx* c) {
     c->X_d = c->lnp_d = nullptr;
     c->nacc_d.reset();
     c->send_d.reset(); c->recv_d.reset();
+    c->exchange = false;
     c->sampler_ready = false;
 }
 
@@ -2609,11 +2494,10 @@ void reset_sampler(vamp_ctx* c) {
 // position + lnprob per row (+ the per-part events when a communicator will run the exchange)
 int ensure_part_events(vamp_ctx* c, int parts);
 int alloc_exchange_buffers(vamp_ctx* c) {
-    const int D = c->regions_h[0].D;
-    HIP_TRY(c->send_d.ensure(vamp::plan::exchange_send_doubles(c->shard_parts, c->part_slots, D)));
-    HIP_TRY(c->recv_d.ensure(vamp::plan::exchange_recv_doubles(c->shard_parts, c->shard_world, c->part_slots, D)));
-    c->part_step.assign(c->shard_parts, 0u);
-    c->part_half.assign(c->shard_parts, 0);
+    HIP_TRY(c->send_d.ensure(vamp::exchange_send_doubles(c)));
+    HIP_TRY(c->recv_d.ensure(vamp::exchange_recv_doubles(c)));
+    vamp::exchange_parts(c);
+    c->exchange = true;
     if (c->comm) return ensure_part_events(c, c->shard_parts);
     return 0;
 }
@@ -2646,7 +2530,7 @@ const std::vector<LaunchClass>& partition_for(const vamp_ctx* c, long long per_r
     return small_ensemble(per_region) ? c->classes_small : c->classes;
 }
 const std::vector<int>& class_of_for(const vamp_ctx* c, long long per_region) {
-    return small_ensemble(per_region) ? c->class_of_small : c->class_of;
+    return small_ensemble(per_region) ? c->plan_small.class_of : c->plan.class_of;
 }
 int class_shape(const vamp_ctx* c, const LaunchClass& cl, long long per_region, long long total, bool packable) {
     if (cl.kind == CK_XL) return SH_XL;
@@ -2660,9 +2544,9 @@ int class_shape(const vamp_ctx* c, const LaunchClass& cl, long long per_region, 
         // (small ensembles never see CK_SMALL2: their partition has the short-region classes merged, partition_for)
         return cl.kind == CK_SMALL2 ? SH_SMALL2 : SH_SMALL;
     }
-    const bool split = cl.kind == CK_WIDE && (c->packing == 256 || (c->packing == 0 && c->min_tiles >= 2 * PARTS));
-    if (split) return c->full_tiles ? SH_SPLIT_FULL : SH_SPLIT;
-    return c->full_tiles ? SH_WIDE_FULL : SH_WIDE;
+    const bool split = cl.kind == CK_WIDE && (c->packing == 256 || (c->packing == 0 && c->plan.min_tiles >= 2 * PARTS));
+    if (split) return c->plan.full_tiles ? SH_SPLIT_FULL : SH_SPLIT;
+    return c->plan.full_tiles ? SH_WIDE_FULL : SH_WIDE;
 }
 
 // the SamplerDev fields every sampler launch shares, the others zero
@@ -2709,7 +2593,7 @@ int join_class(vamp_ctx* c, size_t ci) {
 // stream.  ext: host-supplied draws for `ext_n` movers of `ext_region`.
 int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n, int part = 0) {
     SamplerDev S = sampler_dev(c);
-    if (!ext && c->send_d) {
+    if (!ext && c->exchange) {
         S.pack = c->send_d.get() + (long long)part * c->part_slots * (c->regions_h[0].D + 1);
         c->part_step[part] = (unsigned)c->step;
         c->part_half[part] = half;
@@ -2864,7 +2748,7 @@ long long class_movers(const vamp_ctx* c, const LaunchClass& cl) {
 // (tests, A/B) takes every context the kernel can run.
 bool resident_eligible(const vamp_ctx* c) {
     if (!c->opt_resident || !c->sampler_ready) return false;
-    if (c->shard_world != 1 || c->shard_parts != 1 || c->comm || c->send_d) return false;     // walker-sharded: the exchange is per half-step
+    if (c->shard_world != 1 || c->shard_parts != 1 || c->comm || c->exchange) return false;     // walker-sharded: the exchange is per half-step
     const long long halfW = c->W / 2;
     if (halfW > RES_MAX_MOVERS) return false;
     if (c->opt_resident == 1 && c->n_regions > RES_MAX_REGIONS) return false;
@@ -3035,7 +2919,7 @@ int launch_scatter(vamp_ctx* c, int part, hipStream_t st) {
     const SamplerDev S = sampler_dev(c);
     const long long n_rows = (long long)c->shard_world * c->part_slots;
     const long long own_lo = (long long)c->shard_rank * c->part_slots;
-    const double* recv = c->recv_d.get() + (long long)part * n_rows * (c->regions_h[0].D + 1);
+    const double* recv = c->recv_d.get() + part * vamp::part_doubles(c, true);
     const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
     hipLaunchKernelGGL(k_scatter_rows, dim3(grid), dim3(256), 0, st, S, recv, c->part_step[part], c->part_half[part],
                        (long long)part * c->part_stride, n_rows, own_lo, own_lo + c->part_slots);
@@ -3049,10 +2933,9 @@ int exchange_part(vamp_ctx* c, int part) {
     RcclApi* api = nullptr;
     int rc = rccl_api(&api);
     if (rc) return rc;
-    const long long row = c->regions_h[0].D + 1;
-    const size_t count = (size_t)(c->part_slots * row);
-    const double* send = c->send_d.get() + (long long)part * c->part_slots * row;
-    double* recv = c->recv_d.get() + (long long)part * c->shard_world * c->part_slots * row;
+    const size_t count = vamp::part_doubles(c, false);
+    const double* send = c->send_d.get() + part * count;
+    double* recv = c->recv_d.get() + part * vamp::part_doubles(c, true);
     const bool overlap = c->shard_parts > 1;
     hipStream_t st = overlap ? c->comm_stream : c->stream;
     if (overlap) {
@@ -3063,7 +2946,7 @@ int exchange_part(vamp_ctx* c, int part) {
     }
     rc = c->timing ? c->xtiming.begin(st) : 0;
     if (rc) return rc;
-    const int r_ = api->AllGather(send, recv, count, RCCL_FLOAT64, c->comm, st);
+    const int r_ = api->AllGather(send, recv, count, RCCL_FLOAT64, c->rccl, st);
     if (r_ != 0) return fail(VAMP_ERR_COMM, std::string("ncclAllGather: ") + api->GetErrorString(r_));
     rc = launch_scatter(c, part, st);
     if (rc) return rc;
@@ -3079,21 +2962,21 @@ int half_step_all(vamp_ctx* c, int half) {
     for (int p = 0; p < c->shard_parts; ++p) {
         int rc = launch_half(c, half, false, 0, 0, p);
         if (rc) return rc;
-        if (c->comm && c->send_d) {
+        if (c->comm && c->exchange) {
             rc = exchange_part(c, p);
             if (rc) return rc;
         }
     }
-    if (c->comm && c->send_d && c->shard_parts > 1)
+    if (c->comm && c->exchange && c->shard_parts > 1)
         for (int p = 0; p < c->shard_parts; ++p) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_scatter[p], 0));
     return 0;
 }
 
 int free_comm(vamp_ctx* c) {
-    if (c->comm) {
+    if (c->rccl) {
         RcclApi* api = nullptr;
-        if (rccl_api(&api) == 0) (void)api->CommDestroy(c->comm);
-        c->comm = nullptr;
+        if (rccl_api(&api) == 0) (void)api->CommDestroy(c->rccl);
+        c->rccl = nullptr;
     }
     for (hipEvent_t e : c->ev_kernel) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_scatter) (void)hipEventDestroy(e);
@@ -3101,8 +2984,7 @@ int free_comm(vamp_ctx* c) {
     c->ev_scatter.clear();
     if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
     c->comm_stream = nullptr;
-    c->comm_rank = 0;
-    c->comm_world = 1;
+    vamp::leave_comm(c);
     return 0;
 }
 
@@ -3135,28 +3017,24 @@ long long vampdbg_resident_plan(vamp_ctx* c, int max_classes, long long* rows) {
 
 int vamp_version(void) { return VAMP_ABI_VERSION; }
 
-const char* vamp_last_error(void) { return g_err.c_str(); }
+const char* vamp_last_error(void) { return vamp::last_error().c_str(); }
 
 int vamp_device_count(int* n) {
-    if (!n) return fail(VAMP_ERR_ARG, "vamp_device_count: n is NULL");
+    if (int rc = vamp::check_device_count(n)) return rc;
     HIP_TRY(hipGetDeviceCount(n));
     return VAMP_OK;
 }
 
 int vamp_ctx_create(vamp_ctx** out, int device, int dtype, int wofz_kind) {
-    if (!out) return fail(VAMP_ERR_ARG, "vamp_ctx_create: out is NULL");
-    if (!((dtype == VAMP_F64 && wofz_kind == VAMP_WOFZ_ACCURATE) || (dtype == VAMP_F32 && wofz_kind == VAMP_WOFZ_HUMLICEK_W4)))
-        return fail(VAMP_ERR_ARG, "vamp_ctx_create: supported pairs are (F64, ACCURATE) and (F32, HUMLICEK_W4)");
+    if (int rc = vamp::check_ctx_create(out, dtype, wofz_kind)) return rc;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VAMP_ERR_ARG, "vamp_ctx_create: no such device");
+    if (int rc = vamp::check_device(device, ndev)) return rc;
     HIP_TRY(hipSetDevice(device));
-    vamp_ctx* c = new (std::nothrow) vamp_ctx();
-    if (!c) return fail(VAMP_ERR_NOMEM, "vamp_ctx_create: host allocation failed");
+    vamp_ctx* c = nullptr;
+    if (int rc = vamp::new_ctx(&c, dtype)) return rc;
     c->device = device;
-    c->dtype = dtype;
     c->wofz_kind = wofz_kind;
-    c->f32 = (dtype == VAMP_F32);
     hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -3185,39 +3063,32 @@ int vamp_ctx_destroy(vamp_ctx* c) {
 }
 
 int vamp_ctx_set_stream(vamp_ctx* c, void* hip_stream) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_ctx_set_stream: ctx is NULL");
+    if (int rc = vamp::need_ctx(c, "vamp_ctx_set_stream")) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     return VAMP_OK;
 }
 
 int vamp_ctx_set_stream_default(vamp_ctx* c) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_ctx_set_stream_default: ctx is NULL");
+    if (int rc = vamp::need_ctx(c, "vamp_ctx_set_stream_default")) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->stream = nullptr;       // HIP's legacy default stream: what callers that never create a stream run on
     return VAMP_OK;
 }
 
-int vamp_ctx_set_packing(vamp_ctx* c, int lanes_per_walker) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_ctx_set_packing: ctx is NULL");
-    if (lanes_per_walker != 0 && lanes_per_walker != 16 && lanes_per_walker != 64 && lanes_per_walker != 65 && lanes_per_walker != 256)
-        return fail(VAMP_ERR_ARG, "vamp_ctx_set_packing: lanes_per_walker must be 0 (auto), 16, 64, 65 (64 + per-walker tables) or 256");
-    c->packing = lanes_per_walker;
-    return VAMP_OK;
-}
+int vamp_ctx_set_packing(vamp_ctx* c, int lanes_per_walker) { return vamp::set_packing(c, lanes_per_walker); }
 
 int vamp_ctx_set_option(vamp_ctx* c, const char* name, int64_t value) {
-    if (!c || !name) return fail(VAMP_ERR_ARG, "vamp_ctx_set_option: NULL argument");
+    if (int rc = vamp::check_option(c, name)) return rc;
     const std::string key(name);
     if (key == "map_device") c->opt_map_device = value != 0;
     else if (key == "resident") c->opt_resident = value < 0 ? 0 : value > 2 ? 2 : (int)value;
-    else if (key == "class_streams") c->concurrent_classes = value != 0;
-    else return fail(VAMP_ERR_ARG, "vamp_ctx_set_option: unknown option '" + key + "' (map_device, resident, class_streams)");
+    else c->concurrent_classes = value != 0;
     return VAMP_OK;
 }
 
 int vamp_ctx_synchronize(vamp_ctx* c) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_ctx_synchronize: ctx is NULL");
+    if (int rc = vamp::need_ctx(c, "vamp_ctx_synchronize")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VAMP_OK;
@@ -3226,81 +3097,18 @@ int vamp_ctx_synchronize(vamp_ctx* c) {
 int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const double* x, const double* flux,
                      const double* noise, const int32_t* n_comp, int mode, int sample_sd, int include_norm,
                      const double* bounds, const double* nbz) {
-    if (!c || n_regions <= 0 || !pix_off || !x || !flux || !noise || !n_comp)
-        return fail(VAMP_ERR_ARG, "vamp_set_regions: NULL argument or n_regions <= 0");
-    if (mode != VAMP_GAUSS3 && mode != VAMP_VOIGT4 && mode != VAMP_NBZ3) return fail(VAMP_ERR_ARG, "vamp_set_regions: bad mode");
-    if (mode == VAMP_NBZ3 && !nbz) return fail(VAMP_ERR_ARG, "vamp_set_regions: VAMP_NBZ3 needs nbz");
-    if (pix_off[0] != 0) return fail(VAMP_ERR_ARG, "vamp_set_regions: pix_off[0] must be 0");
-    if (n_regions > 65535) return fail(VAMP_ERR_ARG, "vamp_set_regions: at most 65535 regions per context (one grid row per region)");
+    if (int rc = vamp::check_set_regions(c, n_regions, pix_off, x, flux, noise, n_comp, mode, nbz)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     reset_sampler(c);
     reset_regions(c);
-    const int q = (mode == VAMP_VOIGT4) ? 4 : 3;
-    std::vector<RegionDev> R(n_regions);
-    for (int r = 0; r < n_regions; ++r) {
-        const long long P = pix_off[r + 1] - pix_off[r];
-        if (P < 2 || P > 0x7fffffff) return fail(VAMP_ERR_ARG, "vamp_set_regions: a region needs >= 2 pixels");
-        if (n_comp[r] < 1 || n_comp[r] > KMAX_ALL) return fail(VAMP_ERR_ARG, "vamp_set_regions: n_comp out of range (1..32)");
-        RegionDev d;
-        std::memset(&d, 0, sizeof(d));
-        d.pix_off = pix_off[r];
-        d.P = (int)P;
-        d.K = n_comp[r];
-        d.mode = mode;
-        d.q = q;
-        d.sample_sd = sample_sd ? 1 : 0;
-        d.rng_id = r;
-        d.D = q * d.K + d.sample_sd;
-        d.d_before = r ? R[r - 1].d_before + R[r - 1].D : 0;
-        d.tau_off = r ? R[r - 1].tau_off + (long long)R[r - 1].K * R[r - 1].P : 0;
-        d.sim_off = r ? R[r - 1].sim_off + (long long)(R[r - 1].D + 1) * R[r - 1].D : 0;
-        const double* xr = x + pix_off[r];
-        if (bounds) {
-            d.c_lo = bounds[4 * r + 0];
-            d.c_hi = bounds[4 * r + 1];
-            d.w_max = (mode == VAMP_GAUSS3) ? bounds[4 * r + 2] : bounds[4 * r + 3];
-        } else {
-            d.c_lo = std::min(xr[0], xr[P - 1]);             // vpfits.py:250 (the reference's grid ascends)
-            d.c_hi = std::max(xr[0], xr[P - 1]);
-            const double sigma_max = (d.c_hi - d.c_lo) / 2.0;                         // vpfits.py:320
-            d.w_max = (mode == VAMP_GAUSS3) ? sigma_max : sigma_max * 2 * std::sqrt(2 * std::log(2.0));   // :326
-        }
-        if (!(d.c_hi > d.c_lo) || !(d.w_max > 0)) return fail(VAMP_ERR_ARG, "vamp_set_regions: empty prior range");
-        d.lp_c = -std::log(d.c_hi - d.c_lo);
-        d.lp_w = -std::log(d.w_max);
-        if (mode == VAMP_NBZ3) {
-            d.l_fixed = nbz[4 * r + 0];
-            d.line = nbz[4 * r + 1];
-            d.x_origin = nbz[4 * r + 2];
-            d.x_scale = nbz[4 * r + 3];
-        }
-        double nc = 0.0;
-        if (include_norm && !sample_sd) {
-            for (long long i = 0; i < P; ++i) {
-                const double s = noise[pix_off[r] + i];
-                nc += std::log(2.0 * M_PI * s * s);
-            }
-            nc *= -0.5;
-        }
-        d.norm_const = nc;
-        // the tile code takes a tile's first and last pixel as its extent: the grid of a region must be
-        // strictly monotonic (either direction; the reference sorts to ascending frequency,
-        // vpspectrum.py:274-277) and finite
-        double dxmax = 0.0;
-        const bool up = xr[1] > xr[0];
-        for (long long i = 1; i < P; ++i) {
-            const double dx = xr[i] - xr[i - 1];
-            if (!std::isfinite(dx) || dx == 0.0 || (dx > 0.0) != up)
-                return fail(VAMP_ERR_ARG, "vamp_set_regions: x must be finite and strictly monotonic within a region");
-            dxmax = std::max(dxmax, std::fabs(dx));
-        }
-        d.tile_span = 64.0 * TPIX * dxmax;
-        R[r] = d;
-    }
+    static_assert(KMAX == 16 && KMAX_ALL == 32 && PackSmall::KCAP == 8 && PackSmall2::KCAP == 2 && VAMP_MID_MIN_K == 3 &&
+                  VAMP_MID_MIN_P == 96 && BLEND_MAX_PIXELS == 512 && 64 * TPIX == 256, "vamp::plan::Limits describes these shapes");
+    if (int rc = vamp::build_regions(c, n_regions, pix_off, x, noise, n_comp, mode, sample_sd, include_norm, bounds, nbz, VAMP_F32_TABLES != 0))
+        return rc;
+    const std::vector<RegionDev>& R = c->regions_h;
     const long long N = pix_off[n_regions];
-    std::vector<double> wt(N);
-    for (long long i = 0; i < N; ++i) wt[i] = sample_sd ? 1.0 : 1.0 / noise[i];
+    const std::vector<double> wt = vamp::pixel_weights(N, noise, sample_sd);
     HIP_TRY(c->x_d.ensure(N));
     HIP_TRY(c->f_d.ensure(N));
     HIP_TRY(c->wt_d.ensure(N));
@@ -3321,87 +3129,49 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
     }
     HIP_TRY(c->regions_d.ensure(n_regions));
     HIP_TRY(hipMemcpy(c->regions_d.get(), R.data(), n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
-    {
-        // launch classes (csrc/host_plan.hpp, shared with the host build of this ABI).  Forced packings: one class.
-        // Automatic: contexts that look like a real spectrum (<= 8 lines in every region of <= 16, mean region
-        // <= 128 px) split into the blends worth a wavefront and a set of Taylor tables per walker (>= 3 lines over
-        // 96 .. 512 px: table building costs ~2 near-axis evaluations per line and interval, repaid from ~30 px per
-        // line on), the one- and two-line regions (eight walkers per wavefront) and the rest (four); regions of more
-        // than 16 lines form their own class (plain shape PackXL); everything else is one wide class.
-        vamp::plan::Limits lim;
-        static_assert(KMAX == 16 && KMAX_ALL == 32 && PackSmall::KCAP == 8 && PackSmall2::KCAP == 2 && VAMP_MID_MIN_K == 3 &&
-                      VAMP_MID_MIN_P == 96 && BLEND_MAX_PIXELS == 512 && 64 * TPIX == 256, "vamp::plan::Limits describes these shapes");
-        std::vector<vamp::plan::RegionShape> shp(n_regions);
-        for (int r = 0; r < n_regions; ++r) shp[r] = vamp::plan::RegionShape{R[r].P, R[r].K};
-        vamp::plan::ClassPlan cp;
-        const std::string err = vamp::plan::plan_classes(shp, c->packing, mode == VAMP_GAUSS3, c->f32, VAMP_F32_TABLES != 0, cp, lim);
-        if (!err.empty()) return fail(VAMP_ERR_ARG, "vamp_set_regions: " + err);
-        c->full_tiles = cp.full_tiles;
-        c->min_tiles = cp.min_tiles;
-        c->class_of = cp.class_of;
-        vamp::plan::ClassPlan cs;          // the partition of small ensembles: short-region classes merged
-        (void)vamp::plan::plan_classes(shp, c->packing, mode == VAMP_GAUSS3, c->f32, VAMP_F32_TABLES != 0, cs, lim, true);
-        c->class_of_small = cs.class_of;
-        for (int which = 0; which < 2; ++which) {
-            const vamp::plan::ClassPlan& pl = which ? cs : cp;
-            std::vector<LaunchClass>& part = which ? c->classes_small : c->classes;
-            for (size_t k = 0; k < pl.kind.size(); ++k) part.push_back(LaunchClass{pl.kind[k], pl.regions[k]});
+    // the launch classes of both partitions, with their region lists on the device
+    for (int which = 0; which < 2; ++which) {
+        const vamp::plan::ClassPlan& pl = which ? c->plan_small : c->plan;
+        std::vector<LaunchClass>& part = which ? c->classes_small : c->classes;
+        for (size_t k = 0; k < pl.kind.size(); ++k) part.push_back(LaunchClass{pl.kind[k], pl.regions[k]});
 #if VAMP_LPT
-            // small ensembles: a launch is a few rounds of wavefronts, each a serial chain whose length grows with the region's
-            // lines x pixels; the longest chains go FIRST, so that none starts in the last round (regions are independent and the
-            // draws are keyed by region and walker: the order changes no result)
-            bool reordered = false;
-            if (which == 1 || VAMP_LPT == 2)
-                for (LaunchClass& cl : part) {
-                    std::vector<int> before = cl.regions;
-                    std::stable_sort(cl.regions.begin(), cl.regions.end(), [&](int a, int b) {
-                        return (long long)R[a].K * R[a].P > (long long)R[b].K * R[b].P;
-                    });
-                    reordered = reordered || before != cl.regions;
-                }
-            if (part.size() > 1 || reordered)
+        // small ensembles: a launch is a few rounds of wavefronts, each a serial chain whose length grows with the region's
+        // lines x pixels; the longest chains go FIRST, so that none starts in the last round (regions are independent and the
+        // draws are keyed by region and walker: the order changes no result)
+        bool reordered = false;
+        if (which == 1 || VAMP_LPT == 2)
+            for (LaunchClass& cl : part) {
+                std::vector<int> before = cl.regions;
+                std::stable_sort(cl.regions.begin(), cl.regions.end(), [&](int a, int b) {
+                    return (long long)R[a].K * R[a].P > (long long)R[b].K * R[b].P;
+                });
+                reordered = reordered || before != cl.regions;
+            }
+        if (part.size() > 1 || reordered)
 #else
-            if (part.size() > 1)
+        if (part.size() > 1)
 #endif
-                for (LaunchClass& cl : part) {
-                    HIP_TRY(cl.list_d.ensure(cl.regions.size()));
-                    HIP_TRY(hipMemcpy(cl.list_d.get(), cl.regions.data(), cl.regions.size() * sizeof(int), hipMemcpyHostToDevice));
-                }
-        }
+            for (LaunchClass& cl : part) {
+                HIP_TRY(cl.list_d.ensure(cl.regions.size()));
+                HIP_TRY(hipMemcpy(cl.list_d.get(), cl.regions.data(), cl.regions.size() * sizeof(int), hipMemcpyHostToDevice));
+            }
     }
-    c->regions_h = R;
-    c->mode = mode;
     c->n_regions = n_regions;
     c->n_pix = N;
     return VAMP_OK;
 }
 
 int vamp_set_region_ids(vamp_ctx* c, const int32_t* ids) {
-    if (!c || !ids) return fail(VAMP_ERR_ARG, "vamp_set_region_ids: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_set_region_ids: call vamp_set_regions first");
-    for (int r = 0; r < c->n_regions; ++r)
-        if (ids[r] < 0) return fail(VAMP_ERR_ARG, "vamp_set_region_ids: ids must be >= 0");
+    if (int rc = vamp::set_region_ids(c, ids)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < c->n_regions; ++r) c->regions_h[r].rng_id = ids[r];
     HIP_TRY(hipMemcpy(c->regions_d.get(), c->regions_h.data(), c->n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
     return VAMP_OK;
 }
 
-int vamp_region_class(vamp_ctx* c, int region, int* kind, int* n_classes) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_region_class: ctx is NULL");
-    if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_region_class: no such region");
-    if (kind) *kind = c->classes[c->class_of[region]].kind;
-    if (n_classes) *n_classes = (int)c->classes.size();
-    return VAMP_OK;
-}
+int vamp_region_class(vamp_ctx* c, int region, int* kind, int* n_classes) { return vamp::region_class(c, region, kind, n_classes); }
 
-int vamp_region_ndim(vamp_ctx* c, int region, int* ndim) {
-    if (!c || !ndim) return fail(VAMP_ERR_ARG, "vamp_region_ndim: NULL argument");
-    if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_region_ndim: no such region");
-    *ndim = c->regions_h[region].D;
-    return VAMP_OK;
-}
+int vamp_region_ndim(vamp_ctx* c, int region, int* ndim) { return vamp::region_ndim(c, region, ndim); }
 
 namespace {
 // k_lnprob on device arrays: region >= 0: theta[W, D] of that region -> lnprob[W]; region < 0: every
@@ -3466,28 +3236,19 @@ int lnprob_impl(vamp_ctx* c, int region, int64_t W, const double* theta, double*
 }  // namespace
 
 int vamp_lnprob(vamp_ctx* c, int region, int64_t W, const double* theta, double* lnprob, double* chi2) {
-    if (!c || !theta || !lnprob) return fail(VAMP_ERR_ARG, "vamp_lnprob: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_lnprob: call vamp_set_regions first");
-    if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_lnprob: no such region");
-    if (W <= 0) return fail(VAMP_ERR_ARG, "vamp_lnprob: W must be positive");
+    if (int rc = vamp::check_lnprob(c, region, W, theta, lnprob)) return rc;
     return lnprob_impl(c, region, W, theta, lnprob, chi2);
 }
 
 int vamp_lnprob_all(vamp_ctx* c, int64_t W, const double* theta, double* lnprob, double* chi2) {
-    if (!c || !theta || !lnprob) return fail(VAMP_ERR_ARG, "vamp_lnprob_all: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_lnprob_all: call vamp_set_regions first");
-    if (W <= 0) return fail(VAMP_ERR_ARG, "vamp_lnprob_all: W must be positive");
-    if (c->n_regions > 65535) return fail(VAMP_ERR_ARG, "vamp_lnprob_all: at most 65535 regions per launch");
+    if (int rc = vamp::check_lnprob_all(c, W, theta, lnprob)) return rc;
     RoctxRange range("vamp_lnprob_all");
     return lnprob_impl(c, -1, W, theta, lnprob, chi2);
 }
 
 int vamp_map_all(vamp_ctx* c, const double* theta0, const uint8_t* active, int64_t maxiter, int64_t maxfun, double xtol,
                  double ftol, double* theta_best, double* lnprob_best, double* chi2_best, int64_t* iterations) {
-    if (!c || !theta0 || !theta_best || !lnprob_best) return fail(VAMP_ERR_ARG, "vamp_map_all: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_map_all: call vamp_set_regions first");
-    if (c->n_regions > 65535) return fail(VAMP_ERR_ARG, "vamp_map_all: at most 65535 regions per launch");
-    if (maxiter < 0 || maxfun < 0 || !(xtol >= 0.0) || !(ftol >= 0.0)) return fail(VAMP_ERR_ARG, "vamp_map_all: bad limits");
+    if (int rc = vamp::check_map_all(c, theta0, maxiter, maxfun, xtol, ftol, theta_best, lnprob_best)) return rc;
     RoctxRange range("vamp_map_all");
     if (c->opt_map_device) {
         // every region's whole search in ONE launch per launch class (k_map_search), no per-iteration synchronisation
@@ -3524,22 +3285,14 @@ int vamp_map_all(vamp_ctx* c, const double* theta0, const uint8_t* active, int64
     }
     // the host-driven form (vamp_ctx_set_option "map_device" = 0): csrc/map_search.hpp (scipy fmin's rules; shared with
     // the host build of this ABI), one launch + one synchronisation per iteration of all regions
-    std::vector<int> dims(c->n_regions);
-    std::vector<long long> offs(c->n_regions);
-    for (int r = 0; r < c->n_regions; ++r) {
-        dims[r] = c->regions_h[r].D;
-        offs[r] = c->regions_h[r].d_before;
-    }
-    int rc = vamp::nelder_mead_all(c->n_regions, dims.data(), offs.data(), theta0, active, maxiter, maxfun, xtol, ftol, theta_best,
-                                   iterations, [&](int W, const double* th, double* lp) { return lnprob_impl(c, -1, W, th, lp, nullptr); });
+    int rc = vamp::map_search_host(c, theta0, active, maxiter, maxfun, xtol, ftol, theta_best, iterations,
+                                   [&](int W, const double* th, double* lp) { return lnprob_impl(c, -1, W, th, lp, nullptr); });
     if (rc) return rc;
     return lnprob_impl(c, -1, 1, theta_best, lnprob_best, chi2_best);
 }
 
 int vamp_model(vamp_ctx* c, int region, const double* theta1, double* tau_comp, double* flux_model) {
-    if (!c || !theta1) return fail(VAMP_ERR_ARG, "vamp_model: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_model: call vamp_set_regions first");
-    if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_model: no such region");
+    if (int rc = vamp::check_model(c, "vamp_model", region, theta1)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const RegionDev& R = c->regions_h[region];
     DevBuf<double> th_d, tau_d, fl_d;
@@ -3558,8 +3311,7 @@ int vamp_model(vamp_ctx* c, int region, const double* theta1, double* tau_comp, 
 }
 
 int vamp_model_all(vamp_ctx* c, const double* theta, double* tau_comp, double* flux_model) {
-    if (!c || !theta) return fail(VAMP_ERR_ARG, "vamp_model_all: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_model_all: call vamp_set_regions first");
+    if (int rc = vamp::check_model_all(c, theta)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const RegionDev& last = c->regions_h.back();
     const size_t nth = (size_t)(last.d_before + last.D), ntau = (size_t)(last.tau_off + (long long)last.K * last.P);
@@ -3581,9 +3333,7 @@ int vamp_model_all(vamp_ctx* c, const double* theta, double* tau_comp, double* f
 }
 
 int vamp_line_records(vamp_ctx* c, int region, const double* theta1, double* rec, double* lnprior) {
-    if (!c || !theta1 || !rec || !lnprior) return fail(VAMP_ERR_ARG, "vamp_line_records: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_line_records: call vamp_set_regions first");
-    if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_line_records: no such region");
+    if (int rc = vamp::check_model(c, "vamp_line_records", region, theta1 && rec && lnprior)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const RegionDev& R = c->regions_h[region];
     DevBuf<double> th_d, rec_d;
@@ -3600,7 +3350,7 @@ int vamp_line_records(vamp_ctx* c, int region, const double* theta1, double* rec
 }
 
 int vamp_wofz_re(vamp_ctx* c, int64_t n, const double* x, const double* y, double* re_w) {
-    if (!c || !x || !y || !re_w || n <= 0) return fail(VAMP_ERR_ARG, "vamp_wofz_re: bad argument");
+    if (int rc = vamp::check_wofz(c, n, x, y, re_w)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<double> x_d, y_d, o_d;
     HIP_TRY(x_d.ensure(n));
@@ -3617,7 +3367,7 @@ int vamp_wofz_re(vamp_ctx* c, int64_t n, const double* x, const double* y, doubl
 }
 
 int vamp_sampler_bind_state(vamp_ctx* c, void* X_dev, void* lnp_dev) {
-    if (!c || !X_dev || !lnp_dev) return fail(VAMP_ERR_ARG, "vamp_sampler_bind_state: NULL argument");
+    if (int rc = vamp::check_bind_state(c, X_dev, lnp_dev)) return rc;
     reset_sampler(c);
     c->X_d = (double*)X_dev;
     c->lnp_d = (double*)lnp_dev;
@@ -3625,31 +3375,16 @@ int vamp_sampler_bind_state(vamp_ctx* c, void* X_dev, void* lnp_dev) {
 }
 
 int vamp_sampler_init(vamp_ctx* c, int64_t W, const double* theta0, uint64_t seed, double a, int32_t split_block) {
-    if (!c || !theta0) return fail(VAMP_ERR_ARG, "vamp_sampler_init: NULL argument");
-    if (c->n_regions == 0) return fail(VAMP_ERR_STATE, "vamp_sampler_init: call vamp_set_regions first");
-    if (W < 2 || (W & 1)) return fail(VAMP_ERR_ARG, "vamp_sampler_init: W must be even and >= 2");
-    if (split_block < 2 || (split_block & 1) || W % split_block) return fail(VAMP_ERR_ARG, "vamp_sampler_init: split_block must be even and divide W");
-    if (!(a > 1.0)) return fail(VAMP_ERR_ARG, "vamp_sampler_init: a must be > 1");
+    if (int rc = vamp::check_sampler_init(c, W, theta0, a, split_block)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     RoctxRange range("vamp_sampler_init");
     HIP_TRY(hipStreamSynchronize(c->stream));
-    long long tt = 0;
-    for (int r = 0; r < c->n_regions; ++r) {
-        c->regions_h[r].theta_off = tt;
-        c->regions_h[r].walker_off = (long long)r * W;
-        tt += (long long)W * c->regions_h[r].D;
-    }
+    vamp::init_sampler(c, W, seed, a, split_block);
     HIP_TRY(hipMemcpy(c->regions_d.get(), c->regions_h.data(), c->n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
     const bool bound = c->X_d && c->X_d != c->X_own.get();      // the caller's state (vamp_sampler_bind_state) is kept
     if (!bound) reset_sampler(c);
     c->nacc_d.reset();
-    c->W = W;
-    c->total_theta = tt;
-    c->total_walkers = (long long)c->n_regions * W;
-    c->split_block = split_block;
-    c->a = a;
-    c->seed = seed;
-    c->step = 0;
+    const long long tt = c->total_theta;
     if (!bound) {
         HIP_TRY(c->X_own.ensure(tt));
         HIP_TRY(c->lnp_own.ensure(c->total_walkers));
@@ -3666,51 +3401,17 @@ int vamp_sampler_init(vamp_ctx* c, int64_t W, const double* theta0, uint64_t see
         if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->shard_rank = 0;
-    c->shard_world = 1;
-    c->shard_parts = 1;
-    c->part_slots = c->part_stride = 0;
-    c->slot_begin = 0;
-    c->slot_end = c->total_walkers / 2;
     c->sampler_ready = true;
     return VAMP_OK;
 }
 
 int vamp_sampler_set_shard_parts(vamp_ctx* c, int rank, int world, int parts, int64_t* own_begin, int64_t* own_end) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_sampler_set_shard: ctx is NULL");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_set_shard: call vamp_sampler_init first");
-    if (world < 1 || rank < 0 || rank >= world) return fail(VAMP_ERR_ARG, "vamp_sampler_set_shard: bad rank/world");
-    if (parts < 1 || parts > 64) return fail(VAMP_ERR_ARG, "vamp_sampler_set_shard: parts must be in 1..64");
-    if (c->n_regions != 1) return fail(VAMP_ERR_ARG, "vamp_sampler_set_shard: walker sharding is for single-region contexts (shard regions across devices otherwise)");
-    if (c->comm && (world != c->comm_world || rank != c->comm_rank))
-        return fail(VAMP_ERR_ARG, "vamp_sampler_set_shard: rank/world differ from the communicator's (vamp_comm_init_rank)");
-    // the ensemble is cut into `parts` equal row ranges and each of those into `world` shards (csrc/host_plan.hpp)
-    vamp::plan::ShardPlan sp;
-    {
-        const std::string err = vamp::plan::plan_shard(c->W, c->split_block, rank, world, parts, sp);
-        if (!err.empty()) return fail(VAMP_ERR_ARG, "vamp_sampler_set_shard: " + err);
-    }
-    c->shard_rank = rank;
-    c->shard_world = world;
-    c->shard_parts = parts;
-    c->part_slots = sp.part_slots;
-    c->part_stride = sp.part_stride;
-    c->slot_begin = sp.slot_begin;
-    c->slot_end = c->slot_begin + c->part_slots;      // of part 0
-    // exchange buffers: the movers of every part in slot order, position + lnprob per row
+    if (int rc = vamp::set_shard_parts(c, rank, world, parts, own_begin, own_end)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->send_d.reset();
     c->recv_d.reset();
-    if (world > 1 || c->comm) {
-        int rc = alloc_exchange_buffers(c);
-        if (rc) return rc;
-    }
-    for (int p = 0; p < parts; ++p) {
-        if (own_begin) own_begin[p] = sp.own_begin[p];
-        if (own_end) own_end[p] = sp.own_end[p];
-    }
-    return VAMP_OK;
+    return vamp::needs_exchange(c) ? alloc_exchange_buffers(c) : VAMP_OK;
 }
 
 int vamp_sampler_set_shard(vamp_ctx* c, int rank, int world, int64_t* own_begin, int64_t* own_end) {
@@ -3718,8 +3419,7 @@ int vamp_sampler_set_shard(vamp_ctx* c, int rank, int world, int64_t* own_begin,
 }
 
 int vamp_sampler_state_ptrs(vamp_ctx* c, void** X_dev, void** lnp_dev, int64_t* total_theta, int64_t* total_walkers) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_sampler_state_ptrs: ctx is NULL");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_state_ptrs: call vamp_sampler_init first");
+    if (int rc = vamp::need_sampler(c, "vamp_sampler_state_ptrs")) return rc;
     if (X_dev) *X_dev = c->X_d;
     if (lnp_dev) *lnp_dev = c->lnp_d;
     if (total_theta) *total_theta = c->total_theta;
@@ -3728,9 +3428,7 @@ int vamp_sampler_state_ptrs(vamp_ctx* c, void** X_dev, void** lnp_dev, int64_t* 
 }
 
 int vamp_sampler_half_step(vamp_ctx* c, int half) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step: ctx is NULL");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_half_step: call vamp_sampler_init first");
-    if (half != 0 && half != 1) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step: half must be 0 or 1");
+    if (int rc = vamp::check_half_step(c, half)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     int rc = half_step_all(c, half);
     if (rc) return rc;
@@ -3739,12 +3437,7 @@ int vamp_sampler_half_step(vamp_ctx* c, int half) {
 }
 
 int vamp_sampler_half_step_part(vamp_ctx* c, int half, int part) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_part: ctx is NULL");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_half_step_part: call vamp_sampler_init first");
-    if (half != 0 && half != 1) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_part: half must be 0 or 1");
-    if (part < 0 || part >= c->shard_parts) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_part: no such part");
-    if (c->comm && c->send_d)
-        return fail(VAMP_ERR_STATE, "vamp_sampler_half_step_part: with a communicator the exchange is part of vamp_sampler_half_step / vamp_sampler_run");
+    if (int rc = vamp::check_half_step_part(c, half, part)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     int rc = launch_half(c, half, false, 0, 0, part);
     if (rc) return rc;
@@ -3754,21 +3447,7 @@ int vamp_sampler_half_step_part(vamp_ctx* c, int half, int part) {
 
 int vamp_sampler_half_step_ext(vamp_ctx* c, int region, int64_t n, const int32_t* active_idx, const int32_t* partner_idx,
                                const double* zz, const double* logu) {
-    if (!c || !active_idx || !partner_idx || !zz || !logu) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: NULL argument");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_half_step_ext: call vamp_sampler_init first");
-    if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: no such region");
-    if (n <= 0 || n > c->W) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: bad n");
-    // validate on the host: a wild index would be an out-of-bounds device access
-    std::vector<char> is_active(c->W, 0);
-    for (int64_t i = 0; i < n; ++i) {
-        if (active_idx[i] < 0 || active_idx[i] >= c->W || partner_idx[i] < 0 || partner_idx[i] >= c->W)
-            return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: walker index out of range");
-        if (is_active[active_idx[i]]) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: duplicate active walker");
-        is_active[active_idx[i]] = 1;
-        if (!(zz[i] > 0.0)) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: stretch factor must be positive");
-    }
-    for (int64_t i = 0; i < n; ++i)
-        if (is_active[partner_idx[i]]) return fail(VAMP_ERR_ARG, "vamp_sampler_half_step_ext: partner must belong to the frozen complement");
+    if (int rc = vamp::check_half_step_ext(c, region, n, active_idx, partner_idx, zz, logu)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(c->ext_act_d.ensure(n));
     HIP_TRY(c->ext_par_d.ensure(n));
@@ -3785,12 +3464,7 @@ int vamp_sampler_half_step_ext(vamp_ctx* c, int region, int64_t n, const int32_t
 }
 
 int vamp_sampler_run_dev(vamp_ctx* c, int64_t n_steps, int thin, double* chain_dev, double* lnprob_chain_dev, double* seconds) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_sampler_run_dev: ctx is NULL");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_run_dev: call vamp_sampler_init first");
-    if (n_steps < 0 || thin < 1) return fail(VAMP_ERR_ARG, "vamp_sampler_run_dev: n_steps >= 0 and thin >= 1 required");
-    if (c->shard_world != 1 && !(c->comm && c->send_d))
-        return fail(VAMP_ERR_STATE, "vamp_sampler_run_dev: a sharded context without a communicator is stepped by the host "
-                                    "(half_step_part + pack_get / scatter_put)");
+    if (int rc = vamp::check_run(c, true, n_steps, thin)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     RoctxRange range("vamp_sampler_run");
     const long long n_keep = n_steps / thin;
@@ -3830,9 +3504,7 @@ int vamp_sampler_run_dev(vamp_ctx* c, int64_t n_steps, int thin, double* chain_d
 
 int vamp_sampler_run(vamp_ctx* c, int64_t n_steps, int thin, double* chain, double* lnprob_chain, int64_t* n_accept,
                      double* seconds) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_sampler_run: ctx is NULL");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_run: call vamp_sampler_init first");
-    if (n_steps < 0 || thin < 1) return fail(VAMP_ERR_ARG, "vamp_sampler_run: n_steps >= 0 and thin >= 1 required");
+    if (int rc = vamp::check_run(c, false, n_steps, thin)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const long long n_keep = n_steps / thin;
     DevBuf<double> chain_d, lchain_d;
@@ -3848,7 +3520,7 @@ int vamp_sampler_run(vamp_ctx* c, int64_t n_steps, int thin, double* chain, doub
 
 // ---- walker-sharded multi-GPU runs ------------------------------------------------------------
 int vamp_comm_unique_id(char* id) {
-    if (!id) return fail(VAMP_ERR_ARG, "vamp_comm_unique_id: id is NULL");
+    if (int rc = vamp::check_unique_id(id)) return rc;
     RcclApi* api = nullptr;
     int rc = rccl_api(&api);
     if (rc) return rc;
@@ -3859,12 +3531,7 @@ int vamp_comm_unique_id(char* id) {
 }
 
 int vamp_comm_init_rank(vamp_ctx* c, const char* id, int rank, int world) {
-    if (!c || !id) return fail(VAMP_ERR_ARG, "vamp_comm_init_rank: NULL argument");
-    if (world < 1 || rank < 0 || rank >= world) return fail(VAMP_ERR_ARG, "vamp_comm_init_rank: bad rank/world");
-    if (c->comm) return fail(VAMP_ERR_STATE, "vamp_comm_init_rank: the context already has a communicator");
-    // either order of vamp_sampler_set_shard_parts and vamp_comm_init_rank is accepted, but they must agree
-    if (c->sampler_ready && (c->shard_world != 1 || c->send_d) && (c->shard_world != world || c->shard_rank != rank))
-        return fail(VAMP_ERR_ARG, "vamp_comm_init_rank: rank/world differ from the shard already set (vamp_sampler_set_shard_parts)");
+    if (int rc = vamp::check_comm_init_rank(c, id, rank, world)) return rc;
     RcclApi* api = nullptr;
     int rc = rccl_api(&api);
     if (rc) return rc;
@@ -3876,13 +3543,12 @@ int vamp_comm_init_rank(vamp_ctx* c, const char* id, int rank, int world) {
     std::memcpy(u.internal, id, VAMP_COMM_ID_BYTES);
     void* comm = nullptr;
     RCCL_TRY(api, api->CommInitRank(&comm, world, u, rank));
-    c->comm = comm;
-    c->comm_rank = rank;
-    c->comm_world = world;
+    c->rccl = comm;
+    const bool shard_first = vamp::join_comm(c, rank, world);
     HIP_TRY(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
     // the shard came first: its exchange buffers (a single-rank shard has none yet) and per-part events are due now
-    if (c->sampler_ready && c->n_regions == 1 && c->part_slots > 0) {
-        if (!c->send_d) rc = alloc_exchange_buffers(c);
+    if (shard_first) {
+        if (!c->exchange) rc = alloc_exchange_buffers(c);
         else rc = ensure_part_events(c, c->shard_parts);
         if (rc) return rc;
     }
@@ -3890,14 +3556,13 @@ int vamp_comm_init_rank(vamp_ctx* c, const char* id, int rank, int world) {
 }
 
 int vamp_comm_info(vamp_ctx* c, int* rank, int* world, int* queried) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_comm_info: ctx is NULL");
-    if (!c->comm) return fail(VAMP_ERR_STATE, "vamp_comm_info: the context has no communicator (vamp_comm_init_rank)");
+    if (int rc = vamp::check_comm_info(c)) return rc;
     int r = c->comm_rank, w = c->comm_world, q = 0;
     RcclApi* api = nullptr;
     if (rccl_api(&api) == 0 && api->CommCount && api->CommUserRank) {
         int w2 = 0, r2 = 0;
-        RCCL_TRY(api, api->CommCount(c->comm, &w2));
-        RCCL_TRY(api, api->CommUserRank(c->comm, &r2));
+        RCCL_TRY(api, api->CommCount(c->rccl, &w2));
+        RCCL_TRY(api, api->CommUserRank(c->rccl, &r2));
         r = r2; w = w2; q = 1;
     }
     if (rank) *rank = r;
@@ -3907,7 +3572,7 @@ int vamp_comm_info(vamp_ctx* c, int* rank, int* world, int* queried) {
 }
 
 int vamp_comm_library(char* path, int64_t capacity) {
-    if (!path || capacity < 2) return fail(VAMP_ERR_ARG, "vamp_comm_library: no room for a path");
+    if (int rc = vamp::check_comm_library(path, capacity)) return rc;
     RcclApi* api = nullptr;
     int rc = rccl_api(&api);
     if (rc) return rc;
@@ -3918,7 +3583,7 @@ int vamp_comm_library(char* path, int64_t capacity) {
 }
 
 int vamp_comm_destroy(vamp_ctx* c) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_comm_destroy: ctx is NULL");
+    if (int rc = vamp::need_ctx(c, "vamp_comm_destroy")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->comm_stream) HIP_TRY(hipStreamSynchronize(c->comm_stream));
@@ -3927,22 +3592,18 @@ int vamp_comm_destroy(vamp_ctx* c) {
 }
 
 int vamp_sampler_pack_get(vamp_ctx* c, int part, double* rows) {
-    if (!c || !rows) return fail(VAMP_ERR_ARG, "vamp_sampler_pack_get: NULL argument");
-    if (!c->sampler_ready || !c->send_d) return fail(VAMP_ERR_STATE, "vamp_sampler_pack_get: no sharded sampler (vamp_sampler_set_shard_parts with world > 1)");
-    if (part < 0 || part >= c->shard_parts) return fail(VAMP_ERR_ARG, "vamp_sampler_pack_get: no such part");
+    if (int rc = vamp::check_exchange_rows(c, false, part, rows)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const size_t n = (size_t)c->part_slots * (c->regions_h[0].D + 1);
+    const size_t n = vamp::part_doubles(c, false);
     HIP_TRY(hipMemcpy(rows, c->send_d.get() + (size_t)part * n, n * sizeof(double), hipMemcpyDeviceToHost));
     return VAMP_OK;
 }
 
 int vamp_sampler_scatter_put(vamp_ctx* c, int part, const double* rows_all) {
-    if (!c || !rows_all) return fail(VAMP_ERR_ARG, "vamp_sampler_scatter_put: NULL argument");
-    if (!c->sampler_ready || !c->recv_d) return fail(VAMP_ERR_STATE, "vamp_sampler_scatter_put: no sharded sampler (vamp_sampler_set_shard_parts with world > 1)");
-    if (part < 0 || part >= c->shard_parts) return fail(VAMP_ERR_ARG, "vamp_sampler_scatter_put: no such part");
+    if (int rc = vamp::check_exchange_rows(c, true, part, rows_all)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)c->shard_world * c->part_slots * (c->regions_h[0].D + 1);
+    const size_t n = vamp::part_doubles(c, true);
     HIP_TRY(hipMemcpyAsync(c->recv_d.get() + (size_t)part * n, rows_all, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     int rc = launch_scatter(c, part, c->stream);
     if (rc) return rc;
@@ -3951,8 +3612,7 @@ int vamp_sampler_scatter_put(vamp_ctx* c, int part, const double* rows_all) {
 }
 
 int vamp_sampler_get_state(vamp_ctx* c, double* theta, double* lnprob, int64_t* n_accept, int64_t* step) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_sampler_get_state: ctx is NULL");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_get_state: call vamp_sampler_init first");
+    if (int rc = vamp::need_sampler(c, "vamp_sampler_get_state")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (theta) HIP_TRY(hipMemcpy(theta, c->X_d, c->total_theta * sizeof(double), hipMemcpyDeviceToHost));
@@ -3963,9 +3623,7 @@ int vamp_sampler_get_state(vamp_ctx* c, double* theta, double* lnprob, int64_t* 
 }
 
 int vamp_sampler_set_state(vamp_ctx* c, const double* theta, const double* lnprob, int64_t step) {
-    if (!c || !theta || !lnprob) return fail(VAMP_ERR_ARG, "vamp_sampler_set_state: NULL argument");
-    if (!c->sampler_ready) return fail(VAMP_ERR_STATE, "vamp_sampler_set_state: call vamp_sampler_init first");
-    if (step < 0) return fail(VAMP_ERR_ARG, "vamp_sampler_set_state: step must be >= 0");
+    if (int rc = vamp::check_set_state(c, theta, lnprob, step)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->X_d, theta, c->total_theta * sizeof(double), hipMemcpyHostToDevice));
@@ -3975,7 +3633,7 @@ int vamp_sampler_set_state(vamp_ctx* c, const double* theta, const double* lnpro
 }
 
 int vamp_exchange_timing(vamp_ctx* c, double* total_ms, int64_t* exchanges) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_exchange_timing: ctx is NULL");
+    if (int rc = vamp::need_ctx(c, "vamp_exchange_timing")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     int rc = c->xtiming.flush();
     if (rc) return rc;
@@ -4000,7 +3658,7 @@ int vamp_debug_stamps(unsigned long long* out, int cap) {
 #endif
 
 int vamp_kernel_timing(vamp_ctx* c, int enable, double* total_ms, int64_t* launches) {
-    if (!c) return fail(VAMP_ERR_ARG, "vamp_kernel_timing: ctx is NULL");
+    if (int rc = vamp::need_ctx(c, "vamp_kernel_timing")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     int rc = c->ktiming.flush();
     if (rc) return rc;
