@@ -87,8 +87,9 @@ int vamp_ctx_set_option(vamp_ctx* ctx, const char* name, int64_t value);
  *        fp64, the line cores are read from per-line Taylor tables shared by the workgroup (long regions);
  *   16   four walkers per wavefront, <= 8 components per region (the short regions of real
  *        spectra; draws come from a one-thread-per-mover launch; automatic packing uses eight
- *        walkers per wavefront, 8 lanes each, for regions of one or two components when the launch
- *        fills the chip or the ensemble has 33 .. 128 movers per region);
+ *        walkers per wavefront, 8 lanes each, for regions of one or two components only when the
+ *        launch fills the chip, >= 16 384 movers: a small ensemble, <= 128 movers per region, runs
+ *        them four per wavefront with the other short regions, see 0);
  *   65   64 lanes + the walker's own Taylor tables (four lines' at a time), <= 8 components, no far
  *        field (the blended regions of real spectra: a few lines over a few hundred pixels; regions
  *        of more than 512 pixels fall back to per-pixel evaluation without tables);

@@ -19,6 +19,7 @@ from oracle import vamp_oracle as vo
 import test_gpu_parity as gp
 import test_gpu_vpfit as gv
 import test_gpu_map_classes as gm
+import test_gpu_shape_matrix as gs
 
 # VAMP_CPU_SO: another build of the same library (tests/test_sanitizers.py points it at the ASan/UBSan build)
 CPU_SO = os.environ.get("VAMP_CPU_SO") or os.path.join(ROOT, "oracle", "libvamp_cpu.so")
@@ -336,3 +337,21 @@ def test_point_alone_equals_point_in_a_batch_through_the_host_abi(cpu_lib, case,
 def test_map_search_maxfun_rule_through_the_host_abi(cpu_ctx, case):
     """maxfun is checked at the top of an iteration (tests/test_gpu_map_classes.py::map_maxfun_rule), on the host"""
     gm.map_maxfun_rule(cpu_ctx, case)
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("name", list(gs.ROWS))
+def test_shape_matrix_rows_through_the_host_abi(cpu_lib, name, dtype):
+    """tests/test_gpu_shape_matrix.py's rows at W <= 64 -- dispersed walkers on data with marked pixels against the oracle,
+    the zero-residual check pixel by pixel, four sampler steps -- through the host ABI, which has one arithmetic and no
+    shapes: the rows' inputs satisfy their own conditions and their bars can be met; the launch classes a row expects
+    (vamp_region_class: csrc/host_plan.hpp) are asserted at every upload."""
+    import vamp_amd
+
+    def mk(dt, packing):
+        ctx = vamp_amd.HipContext(dtype=vamp_amd.F64 if dt == "f64" else vamp_amd.F32, lib=cpu_lib)
+        ctx.set_packing(packing)
+        return ctx
+
+    w1, w2 = gs.host_abi_row(mk, name, dtype)
+    print("shape matrix through the host ABI %s %s: dispersed error / bar %.3g, zero-residual sqrt(chi2) %.3g" % (name, dtype, w1, w2))

@@ -38,10 +38,11 @@ def test_boundary_tests_under_asan_ubsan(asan_env):
     """error codes and call order, pack / scatter, the single-rank exchange rehearsal, Philox
     trajectories, injected draws, smallest shapes, the MAP search, regions of 17 .. 32 lines (the stack arrays
     sized by VAMP_MAX_COMPONENTS), the launch / shard plan arithmetic shared with the product
-    (csrc/host_plan.hpp): tests/test_cpu_boundary.py against the instrumented library"""
+    (csrc/host_plan.hpp), the rows of tests/test_gpu_shape_matrix.py (regions of up to 4113 pixels, walkers outside the prior
+    at random positions): tests/test_cpu_boundary.py against the instrumented library"""
     sel = ("error_codes or pack_and_scatter or single_rank or philox or injected_draws or smallest_shapes "
            "or map_all or exports_the_whole_header or lnprob_matches_golden or regions_of_more_than_16_lines or batched_find_bic "
-           "or host_plan")
+           "or host_plan or shape_matrix")
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_cpu_boundary.py"), "-x", "-q",
                           "-p", "no:cacheprovider", "-k", sel], env=asan_env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]

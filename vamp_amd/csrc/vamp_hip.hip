@@ -2548,6 +2548,20 @@ int class_shape(const vamp_ctx* c, const LaunchClass& cl, long long per_region, 
     if (split) return c->plan.full_tiles ? SH_SPLIT_FULL : SH_SPLIT;
     return c->plan.full_tiles ? SH_WIDE_FULL : SH_WIDE;
 }
+// movers of one launch of class `cl` when every region holds `per_region` movers (what decides the class's shape): a
+// single-region ensemble is one launch of its movers -- a shard or a piece of it takes the shape of the whole
+long long class_movers(const vamp_ctx* c, const LaunchClass& cl, long long per_region) {
+    return c->n_regions == 1 ? per_region : (long long)cl.regions.size() * per_region;
+}
+// the shape class `cl` runs in for `per_region` movers per region: the one rule behind the sampler's launches
+// (launch_half, run_resident), vamp_lnprob(_all) and the MAP search (and the test hook vampdbg_launch_plan)
+int launch_shape(const vamp_ctx* c, const LaunchClass& cl, long long per_region) {
+    return class_shape(c, cl, per_region, class_movers(c, cl, per_region), true);
+}
+// movers per region the entry points ask with.  W points per region are W/2 movers of a W-walker ensemble: the sampler's
+// own initial log-posteriors, and a caller's walker checks, run the classes and shapes the ensemble will be stepped in
+inline long long lnprob_movers(long long W) { return (W + 1) / 2; }
+constexpr long long MAP_MOVERS = 1;      // the MAP search: the shape vamp_lnprob runs a single point in
 
 // the SamplerDev fields every sampler launch shares, the others zero
 SamplerDev sampler_dev(const vamp_ctx* c) {
@@ -2641,7 +2655,7 @@ int launch_half(vamp_ctx* c, int half, bool ext, int ext_region, long long ext_n
         const hipStream_t st = (fork && ci > 0) ? c->cls_stream[ci - 1] : c->stream;
         S.region_list = cl.list_d.get();
         // (a shard or a piece of a single-region ensemble takes the shape of the WHOLE ensemble)
-        const int shape = class_shape(c, cl, ext ? n : halfW, (!ext && c->n_regions == 1) ? halfW : n, packable);
+        const int shape = ext ? class_shape(c, cl, n, n, packable) : launch_shape(c, cl, halfW);
         unsigned grid = (unsigned)((n + shape_walkers_per_block(shape) - 1) / shape_walkers_per_block(shape));
         S.wpr = S.bpr = 0;
         S.n_cls_regions = (int)cl.regions.size();
@@ -2735,10 +2749,6 @@ long long resident_lds(int nw) {
     if constexpr (PK::SPLIT && PK::WPB > 1) return 0;
     else return (long long)ResLayout<F32, MODE, PK>::total(nw);
 }
-// movers of one half-step launch of class `cl` on the launch-per-half-step path (what decides its shape)
-long long class_movers(const vamp_ctx* c, const LaunchClass& cl) {
-    return c->n_regions == 1 ? c->W / 2 : (long long)cl.regions.size() * (c->W / 2);
-}
 // every launch class of the context can run its regions' step loops inside one launch each
 // Policy (opt_resident = 1; measured, profiles/r04_c_small_ensembles.txt).  A resident workgroup removes the dispatch
 // gap of a launch per half-step (~5 us of ~16) but serialises its region on ONE compute unit, so it pays only where
@@ -2753,7 +2763,7 @@ bool resident_eligible(const vamp_ctx* c) {
     if (halfW > RES_MAX_MOVERS) return false;
     if (c->opt_resident == 1 && c->n_regions > RES_MAX_REGIONS) return false;
     for (const LaunchClass& cl : partition_for(c, halfW)) {
-        const int shape = class_shape(c, cl, halfW, class_movers(c, cl), true);
+        const int shape = launch_shape(c, cl, halfW);
         const int nw = resident_waves_for(c, shape, halfW);
         if (!vamp::plan::resident_class_ok(cl.kind, halfW, nw, (int)(shape_walkers_per_block(shape) / shape_waves(shape)), c->opt_resident == 1))
             return false;
@@ -2776,7 +2786,7 @@ int run_resident(vamp_ctx* c, long long n_steps, int thin, double* chain_dev, do
         const LaunchClass& cl = classes[ci];
         const hipStream_t st = (fork && ci > 0) ? c->cls_stream[ci - 1] : c->stream;
         S.region_list = cl.list_d.get();
-        const int shape = class_shape(c, cl, halfW, class_movers(c, cl), true);     // the shape launch_half runs this class in
+        const int shape = launch_shape(c, cl, halfW);     // the shape launch_half runs this class in
         const int nw = resident_waves_for(c, shape, halfW);
         const dim3 grid((unsigned)cl.regions.size()), threads(64u * (unsigned)(nw + 1));
         VAMP_FOR_MODE_PK(c->f32, c->mode, shape, rc = launch_resident<F32, M, PK>(c->device, grid, threads, nw, st, S, px, (unsigned)c->step,
@@ -3002,7 +3012,7 @@ long long vampdbg_resident_plan(vamp_ctx* c, int max_classes, long long* rows) {
     const std::vector<LaunchClass>& classes = partition_for(c, halfW);
     for (size_t ci = 0; ci < classes.size() && (int)ci < max_classes; ++ci) {
         const LaunchClass& cl = classes[ci];
-        const int shape = class_shape(c, cl, halfW, class_movers(c, cl), true);
+        const int shape = launch_shape(c, cl, halfW);
         const int nw = resident_waves_for(c, shape, halfW);
         long long lds = 0;
         VAMP_FOR_MODE_PK(c->f32, c->mode, shape, lds = resident_lds<F32, M, PK>(nw));
@@ -3013,6 +3023,37 @@ long long vampdbg_resident_plan(vamp_ctx* c, int max_classes, long long* rows) {
         row[3] = lds;
     }
     return (long long)classes.size();
+}
+
+// Test hook, not part of the header: the launches an entry point makes for `movers_per_region` movers per region (a W-walker
+// ensemble: W / 2; W points of vamp_lnprob(_all): (W + 1) / 2; ignored by the MAP search, which asks with one).  entry 0:
+// the sampler's half-step (and the resident loop), 1: vamp_lnprob_all, 2: vamp_lnprob(region), 3: the device MAP search.
+// One row of {class kind, shape (enum Shape), walkers per workgroup, threads per workgroup, regions of the class} per launch
+// class, at most max_classes rows; region >= 0: only the class of that region (entry 2 needs one).  Returns the number of
+// rows, or an error code.
+long long vampdbg_launch_plan(vamp_ctx* c, long long movers_per_region, int entry, int region, int max_classes, long long* rows) {
+    if (!c || !rows || max_classes < 0 || entry < 0 || entry > 3 || movers_per_region < 1) return fail(VAMP_ERR_ARG, "vampdbg_launch_plan: bad argument");
+    if (c->regions_h.empty()) return fail(VAMP_ERR_STATE, "vampdbg_launch_plan: call vamp_set_regions first");
+    if (region >= c->n_regions || (entry == 2 && region < 0)) return fail(VAMP_ERR_ARG, "vampdbg_launch_plan: no such region");
+    const long long per = entry == 3 ? MAP_MOVERS : movers_per_region;
+    const std::vector<LaunchClass>& classes = partition_for(c, per);
+    const std::vector<int>& class_of = class_of_for(c, per);
+    long long n = 0;
+    for (size_t ci = 0; ci < classes.size(); ++ci) {
+        const LaunchClass& cl = classes[ci];
+        if (region >= 0 && class_of[region] != (int)ci) continue;
+        if (n < max_classes) {
+            const int shape = launch_shape(c, cl, per);
+            long long* row = rows + 5 * n;
+            row[0] = cl.kind;
+            row[1] = shape;
+            row[2] = shape_walkers_per_block(shape);
+            row[3] = shape_threads(shape);
+            row[4] = (long long)cl.regions.size();
+        }
+        ++n;
+    }
+    return n;
 }
 
 int vamp_version(void) { return VAMP_ABI_VERSION; }
@@ -3179,16 +3220,16 @@ namespace {
 // per launch class (blockIdx.y walks the class's region list)
 int launch_lnprob(vamp_ctx* c, int region, long long W, const double* th_d, double* lp_d, double* ch_d) {
     const bool all = region < 0;
-    const bool packable = true;      // one region per block row: every wave lies inside one region
-    // W points per region are W/2 movers of a W-walker ensemble: the sampler's own initial log-posteriors, and a caller's
-    // walker checks, run the classes and shapes the ensemble will be stepped in
-    const long long per = (W + 1) / 2;
+    // (one region per block row: every wave lies inside one region, so every class may pack)
+    const long long per = lnprob_movers(W);
     const std::vector<LaunchClass>& classes = partition_for(c, per);
     const std::vector<int>& class_of = class_of_for(c, per);
     for (size_t ci = 0; ci < classes.size(); ++ci) {
         const LaunchClass& cl = classes[ci];
         if (!all && class_of[region] != (int)ci) continue;
-        const int shape = class_shape(c, cl, per, all ? per * (long long)cl.regions.size() : per, packable);
+        // the class's movers are counted as the sampler counts them, for one region too: a point has the same lnprob
+        // bits through vamp_lnprob(region), vamp_lnprob_all and the sampler that steps it
+        const int shape = launch_shape(c, cl, per);
         const long long per_block = shape_walkers_per_block(shape);
         const dim3 grid((unsigned)((W + per_block - 1) / per_block), all ? (unsigned)cl.regions.size() : 1u);
         const dim3 threads(shape_threads(shape));
@@ -3225,7 +3266,6 @@ int lnprob_impl(vamp_ctx* c, int region, int64_t W, const double* theta, double*
     HIP_TRY(c->sc_chi.ensure(nout));
     double *th_d = c->sc_th.get(), *lp_d = c->sc_lp.get(), *ch_d = chi2 ? c->sc_chi.get() : nullptr;
     HIP_TRY(hipMemcpyAsync(th_d, theta, nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // (the shape must not depend on `all`: a point has the same lnprob bits through either entry)
     int rc = launch_lnprob(c, region, W, th_d, lp_d, ch_d);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(lnprob, lp_d, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -3264,11 +3304,11 @@ int vamp_map_all(vamp_ctx* c, const double* theta0, const uint8_t* active, int64
         HIP_TRY(hipMemcpyAsync(c->map_th_d.get(), theta0, nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
         if (active) HIP_TRY(hipMemcpyAsync(c->map_act_d.get(), active, nr, hipMemcpyHostToDevice, c->stream));
         const unsigned char* act_d = active ? c->map_act_d.get() : nullptr;
-        const std::vector<LaunchClass>& classes = partition_for(c, 1);
+        const std::vector<LaunchClass>& classes = partition_for(c, MAP_MOVERS);
         for (size_t ci = 0; ci < classes.size(); ++ci) {
             const LaunchClass& cl = classes[ci];
             // the shape vamp_lnprob runs a single point of this class in: the objective has the same bits
-            const int shape = class_shape(c, cl, 1, 1, true);
+            const int shape = launch_shape(c, cl, MAP_MOVERS);
             const dim3 grid((unsigned)cl.regions.size()), threads(shape_threads(shape));
             VAMP_FOR_MODE_PK(c->f32, c->mode, shape, hipLaunchKernelGGL((k_map_search<F32, M, PK>), grid, threads, 0, c->stream, c->regions_d.get(),
                                                                     c->pix(), (const int*)cl.list_d.get(), c->map_th_d.get(), act_d, (long long)maxiter,
