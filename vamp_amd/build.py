@@ -26,6 +26,13 @@ DIAG_OUT = os.path.join(HERE, "libvamp_diag.so")
 DIAG_DEPS = [DIAG_SRC, os.path.join(HERE, "..", "include", "vamp_diag.h")]
 DIAG_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
 
+# libvamp_post.so (include/vamp_post.h): the posterior summaries, a third library on the same terms; it shares
+# voigt_math.hpp with the main library, so an edit of the evaluator rebuilds both
+POST_SRC = os.path.join(HERE, "csrc", "posterior.hip")
+POST_OUT = os.path.join(HERE, "libvamp_post.so")
+POST_DEPS = [POST_SRC, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "..", "include", "vamp_post.h")]
+POST_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
+
 
 def _compile(out, src, deps, flags, force, verbose):
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
@@ -43,9 +50,16 @@ def build_diag(force=False, verbose=True):
     return _compile(DIAG_OUT, DIAG_SRC, DIAG_DEPS, DIAG_FLAGS, force, verbose)
 
 
+def build_post(force=False, verbose=True, out=None, defines=()):
+    """libvamp_post.so; returns its path.  ``out`` / ``defines``: a variant build beside it (tools/bench_post.py
+    compares the orientations of the scratch and the 16-lane form)."""
+    return _compile(out or POST_OUT, POST_SRC, POST_DEPS, POST_FLAGS + ["-D" + d for d in defines], force, verbose)
+
+
 def build(force=False, verbose=True):
-    """Both libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
+    """The three libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
     build_diag(force=force, verbose=verbose)
+    build_post(force=force, verbose=verbose)
     return _compile(OUT, SRC, DEPS, FLAGS, force, verbose)
 
 

@@ -8,7 +8,8 @@ branch, do_vamp.py:64-96, calls an undefined function and never ran); worker r r
 ``r % gpus`` and pins it with HIP_VISIBLE_DEVICES before anything in that process touches HIP.
 Spectra are independent: no communication.  New flags: --walkers, --iterations, --burn, --thin,
 --seed, --batched, --gpus (GPUs to use; default: the GPUs this process can see), --dtype {f64,f32}
-(per-pixel arithmetic; $VAMP_DTYPE overrides the default), --backend hip ($VAMP_BACKEND).
+(per-pixel arithmetic; $VAMP_DTYPE overrides the default), --backend hip ($VAMP_BACKEND), --posterior (also write
+``<prefix>posterior.h5``: the posterior flux band and equivalent widths with credible intervals, vamp_amd.posterior).
 """
 import argparse
 import glob
@@ -81,6 +82,12 @@ def fit_one(path, args, device=0):
     t0 = time.perf_counter()
     params = spec.fit_spectrum(batched=args.batched)
     rec = perf_record(spec, path, time.perf_counter() - t0, args.batched)
+    if getattr(args, "posterior", False):
+        t1 = time.perf_counter()
+        post = spec.posterior_summaries()
+        if args.output_folder is not None and getattr(spec, "output_filename", None):
+            spec.write_posterior(post)
+        rec["posterior_seconds"] = time.perf_counter() - t1
     print("vamp_perf " + json.dumps(rec), flush=True)
     if args.output_folder is not None and getattr(spec, "output_filename", None):
         with open(spec.output_filename + "perf.json", "w") as fh:
@@ -120,6 +127,9 @@ def main(argv=None, _fit_name="vamp_amd.do_vamp:fit_one"):
                         "oracle/libvamp_cpu.so is test infrastructure")
     p.add_argument("--batched", action="store_true",
                    help="fit all regions of a spectrum together (one kernel launch per half-step for the whole spectrum)")
+    p.add_argument("--posterior", action="store_true",
+                   help="also summarise the chains of the kept fits on the GPU: posterior band of the fitted flux and equivalent "
+                        "widths with credible intervals, written to <prefix>posterior.h5 (off by default)")
     args = p.parse_args(argv)
     if args.backend != "hip":            # (argparse does not check a default taken from the environment)
         sys.exit("do_vamp: backend %r is not available: the product runs on libvamp_hip.so only (no CPU fallback)" % args.backend)

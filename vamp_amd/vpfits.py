@@ -81,6 +81,7 @@ class _EnsembleMCMC:
         self.walker_steps_per_second = None
         self._thin = 1             # sampler steps per kept sample
         self._diag = None          # ChainDiagnostics of the device-unit chain, computed once
+        self._post = {}            # probs -> PosteriorSummary of the device-unit chain at unit pixel width
 
     def sample(self, iter, burn=0, thin=1, progress_bar=False, **_ignored):
         self._fit._run_sampler(int(iter), int(burn), int(thin))
@@ -129,6 +130,52 @@ class _EnsembleMCMC:
 
     def _set_diagnostics(self, record):
         self._diag = record
+
+    def _posterior(self, probs):
+        """the fit's PosteriorSummary at unit pixel width for ``probs`` (vamp_amd.posterior), computed once per fit and
+        set of probabilities from the fit's ``_chain_dev``, ``_x``, ``_n``, ``_mode`` and ``_sample_sd``"""
+        from . import posterior
+        key = tuple(float(p) for p in np.atleast_1d(posterior.DEFAULT_PROBS if probs is None else probs))
+        if key not in self._post:
+            fit = self._fit
+            if fit._chain_dev is None:
+                raise RuntimeError("no chain: run the sampler first")
+            _, recs = posterior.fits_posterior([fit], probs=key, device=fit.device)
+            if key not in self._post:          # (fits_posterior fills the cache)
+                self._set_posterior(recs[0])
+        return self._post[key]
+
+    def _set_posterior(self, record):
+        self._post[tuple(float(p) for p in record.probs)] = record
+
+    def flux_band(self, probs=None):
+        """The posterior band of the model flux, in the fit's pixel order: {'mean': [P], 'sd': [P], 'quantiles':
+        {p: [P]}} over the kept samples of the whole ensemble (what PyMC's stats() gave for the traced ``total``);
+        ``probs`` defaults to (0.025, 0.16, 0.5, 0.84, 0.975).  One GPU call, cached per fit."""
+        r = self._posterior(probs)
+        return {"mean": r.flux_mean.copy(), "sd": r.flux_sd.copy(),
+                "quantiles": {float(p): r.flux_q[i].copy() for i, p in enumerate(r.probs)}}
+
+    def equivalent_widths(self, wavelengths, probs=None):
+        """Equivalent width of the region and of every line with credible intervals: {'EW': rec, 'components':
+        [rec_k], 'pixel_width', 'n_used', 'n_bad'}, rec = {'mean', 'sd', 'quantiles': {p: value}}.  The pixel width is
+        |lambda_last - lambda_first| / (P - 1), the rule of ``EquivalentWidthFlux``, for the region AND for its lines.
+        (The harvest's per-line point estimates differ in scale: vpspectrum.py:426 passes two edges to
+        ``EquivalentWidthTau`` and so multiplies a line's decrement sum by the whole region width; that quirk of the
+        reference stays in ``_harvest`` and is not reproduced here.)  Cached per fit with ``flux_band``."""
+        r = self._posterior(probs)
+        lam = np.asarray(wavelengths, dtype=np.float64)
+        if lam.size != r.flux_mean.size:
+            raise ValueError("one wavelength per pixel of the fit is required")
+        width = float(np.abs(lam[-1] - lam[0]) / max(1, lam.size - 1))
+
+        def rec(mean, sd, q):
+            return {"mean": float(mean) * width, "sd": float(sd) * width,
+                    "quantiles": {float(p): float(v) * width for p, v in zip(r.probs, q)}}
+
+        return {"EW": rec(r.ew_mean, r.ew_sd, r.ew_q),
+                "components": [rec(r.comp_ew_mean[k], r.comp_ew_sd[k], r.comp_ew_q[k]) for k in range(len(r.comp_ew_mean))],
+                "pixel_width": width, "n_used": r.n_used, "n_bad": r.n_bad}
 
 
 class _Stats(Mapping):
@@ -447,6 +494,7 @@ class VPfit():
         mc_ = self.mcmc
         mc_._flat, mc_._names, mc_._derived = flat, list(self._names), {}
         mc_._thin, mc_._diag = max(1, int(thin)), None
+        mc_._post = {}
         if self._voigt:      # the reference's callers ask for est_sigma_k in Voigt mode too (vpspectrum.py:400)
             for k in range(self._n):
                 mc_._derived["est_sigma_%d" % k] = ("est_G_%d" % k, self.GaussianWidth)

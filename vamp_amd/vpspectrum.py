@@ -407,6 +407,54 @@ class VPspectrum():
         for k in range(n):
             pr['EW'] = np.append(pr['EW'], EquivalentWidthTau(fit.estimated_profiles[k].value, [waves[0], waves[-1]]))
 
+    def posterior_summaries(self, probs=None, scratch_bytes=0):
+        """After ``fit_spectrum``: the posterior band of the fitted flux and the equivalent widths with credible intervals,
+        from ONE GPU call over the kept fits (vamp_amd.posterior).  A dict in wavelength order (flipped like ``_harvest``):
+        ``probs`` [Q]; ``total_mean`` / ``total_sd`` [n_pixels] and ``total_q`` [Q, n_pixels] (1 / 0 / 1 outside regions);
+        ``EW_mean`` / ``EW_sd`` [n_regions] and ``EW_q`` [n_regions, Q]; ``line_EW_mean`` / ``line_EW_sd`` [n_lines] and
+        ``line_EW_q`` [n_lines, Q] in the order of ``params['EW']``.  Every width is the region's pixel width
+        |lambda_last - lambda_first| / (P - 1) (``EquivalentWidthFlux``'s rule), for lines too."""
+        from . import posterior
+        probs = np.atleast_1d(np.asarray(posterior.DEFAULT_PROBS if probs is None else probs, dtype=np.float64))
+        Q, npx, regs = probs.size, len(self.flux_array), self.regions
+        widths = []
+        for start, end in self.region_pixels:
+            lam = self.wavelength_array[start:end]
+            widths.append(float(np.abs(lam[-1] - lam[0]) / max(1, len(lam) - 1)))
+        have, recs = posterior.fits_posterior([r.fit for r in regs], probs=probs, pixel_width=widths, device=getattr(self, "device", 0),
+                                              scratch_bytes=scratch_bytes)
+        if len(have) != len(regs):
+            raise RuntimeError("posterior_summaries: %d of %d regions have no chain" % (len(regs) - len(have), len(regs)))
+        out = {"probs": probs, "total_mean": np.ones(npx), "total_sd": np.zeros(npx), "total_q": np.ones((Q, npx)),
+               "EW_mean": np.array([r.ew_mean for r in recs]), "EW_sd": np.array([r.ew_sd for r in recs]),
+               "EW_q": np.array([r.ew_q for r in recs]).reshape(len(recs), Q),
+               "line_EW_mean": np.concatenate([r.comp_ew_mean for r in recs] or [np.zeros(0)]),
+               "line_EW_sd": np.concatenate([r.comp_ew_sd for r in recs] or [np.zeros(0)]),
+               "line_EW_q": np.concatenate([r.comp_ew_q for r in recs] or [np.zeros((0, Q))], axis=0),
+               "time_step": np.array([r.step for r in recs], dtype=np.int32)}
+        for (start, end), r in zip(self.region_pixels, recs):
+            out["total_mean"][start:end] = np.flip(r.flux_mean, 0)
+            out["total_sd"][start:end] = np.flip(r.flux_sd, 0)
+            out["total_q"][:, start:end] = np.flip(r.flux_q, 1)
+        return out
+
+    def write_posterior(self, post):
+        """``posterior_summaries()``' dict as ``<prefix>posterior.h5``, through h5py when it is importable, else through
+        vamp_amd/h5min.py, as ``write_file`` does; returns the path"""
+        path = self.output_filename + 'posterior.h5'
+        try:
+            import h5py
+        except ImportError:
+            h5py = None
+        if h5py is not None:
+            with h5py.File(path, 'a') as f:
+                for p in post.keys():
+                    f.create_dataset(p, data=np.array(post[p]))
+        else:
+            from . import h5min
+            h5min.write(path, {k: np.array(v) for k, v in post.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
