@@ -254,6 +254,7 @@ using PackMid = Pack<64, 8, true, VAMP_MID_WAVES, true, true, false>;
 using PackXL = Pack<64, KMAX_ALL, true, 2, false, false, false>;
 
 constexpr int FF_NODES = 16;          // Chebyshev nodes of the far-field interpolant of one tile
+constexpr int FF_BATCH = 4;           // tiles of a wavefront whose lines are classified in one 64-lane pass
 #ifndef VAMP_FF_DIST
 #define VAMP_FF_DIST 2.0        // (round 4: was 4.  The series reproduce a wing from 2 half-widths to 3e-11 of ITS value there,
                                 //  tests/test_ff_matrix.py; on well-fitted data with strong damped wings the log-posterior moves
@@ -274,11 +275,13 @@ struct alignas(16) TileScratch {   // per wavefront: far-field working set of th
     double coef[FF_ROWS];   // optical depth of the far lines at the tile's 16 Chebyshev nodes, then (every lane has
                             // read the node values by then) the tile's four local power series, one per quarter,
                             // 14 coefficients each; fp32 contexts store those as floats in the same space
-    int farlist[KMAX];      // lines treated through the far field, as byte offsets of their records (fp64: LineRec,
-                            // fp32: linef rows) -- the list is read four times per tile, an index would cost a
-                            // quarter-rate 32-bit multiply each time
-    int widelist[KMAX];     // near lines far WIDER than the tile (fp64 tables shape): line indices
+    // the lists of the FF_BATCH tiles classified together (ff_classify_batch), one row per tile, as line indices in
+    // bytes: the same 128 B as one tile's two lists of ints; a reader scales the index by its record size with a
+    // full-rate 24-bit multiply
+    unsigned char farlist[FF_BATCH][KMAX];    // lines treated through the far field: deep ones first, then the others, each in line order
+    unsigned char widelist[FF_BATCH][KMAX];   // near lines far WIDER than the tile, or between far and near (fp64 tables shape), in line order
 };
+static_assert(KMAX == 16 && FF_BATCH * KMAX == 64, "lane 16 j + k classifies line k against tile j of a batch");
 // Taylor tables of the near-axis zone of every line of ONE walker (voigt_math.hpp): 28 KiB, which
 // only a workgroup that serves a single walker can afford (4 workgroups per CU).
 template <int NDBL>
@@ -825,22 +828,55 @@ __device__ __forceinline__ void ff_eval2(const double (&Xin)[2], const double (&
 }
 
 // far-field steps shared by the fp64 and the fp32 sweep.  All wave-uniform in control flow.
-// (a) classification of all lines at once: far = centre >= FF_DIST half-widths beyond the tile's
-//     edge and the whole tile outside |z|^2 < 64 of that line; compacted list -> Sx.farlist
-//     (my_w25: half-width of |z|^2 < 625; far lines that reach into it at the tile's edge need the
-//     deep fractions and are listed first)
-template <int FARLIST_SCALE>       // bytes per line record of the list's readers
-__device__ __forceinline__ unsigned long long ff_classify(TileScratch& Sx, int K, int lane, double my_c, double my_w8,
-                                                          double my_w25, double mid, double half) {
+// (a) classification of all lines against the wavefront's next FF_BATCH tiles (base, base + stride, ...) at once: lane
+//     16 j + k holds line k and tile j.  far = centre >= FF_DIST half-widths beyond the tile's edge and the whole
+//     tile outside |z|^2 < 64 of that line (fp32 contexts: outside the line's Gaussian core, VAMP_F32_FAR_CORE); far
+//     lines that reach into |z|^2 < 625 at the tile's edge need the deep fractions and are listed first.  WIDE: near
+//     lines far wider than the tile (`wide_all`), and lines FF_DIST half-widths away whose |z| < 8 zone still reaches
+//     into the tile while their Gaussian core does not (VAMP_MID_NODES), go to the wide list.
+//     Returns the masks of the four tiles, 16 bits each (tile j in bits 16 j ..), and leaves the compacted lists in
+//     Sx.farlist[j] / Sx.widelist[j]; a tile at or past base1 classifies the first tile again and is never consumed.
+//     A pure function of (line record, tile edges): it used to run once per tile on 16 of the 64 lanes.
+__device__ __forceinline__ unsigned ff_tile_field(unsigned long long batchmask, int lane) {   // the 16 bits of this lane's tile
+    const unsigned h = (lane & 32) ? (unsigned)(batchmask >> 32) : (unsigned)batchmask;
+    return (h >> (lane & 16)) & 0xffffu;
+}
+template <bool WIDE, bool F32, class LDS, class xreal>
+__device__ __forceinline__ void ff_classify_batch(const LDS& L, TileScratch& Sx, const xreal* __restrict__ x, int K, int lane_, int base,
+                                                  int base1, int stride, unsigned wide_all,
+                                                  unsigned long long& farmasks, unsigned long long& widemasks) {
+    // everything a lane derives from its index is derived here, once per batch, from an opaque copy: hoisted out of
+    // the tile loop these values would sit in registers the loop does not have (and come back from scratch)
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    const int j = lane >> 4, k = lane & (KMAX - 1);
+    const unsigned below = (1u << k) - 1u;
+    int bj = base + j * stride;
+    bj = bj < base1 ? bj : base;
+    const double x_lo = (double)x[bj], x_hi = (double)x[bj + 64 * TPIX - 1];
+    const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
+    // centre and zone half-widths of "its" line: four LDS reads per batch, all issued together (no short-circuit
+    // evaluation below: the predicates are bit operations on compare results, the pass has no branches but the writes)
+    const LineRec& me = *reinterpret_cast<const LineRec*>(reinterpret_cast<const char*>(L.line) +
+                                                          __umul24((unsigned)(k < K ? k : 0), (unsigned)sizeof(LineRec)));
+    const double my_c = me.c, my_w8 = me.w8, my_w25 = me.w25, my_wmid = me.wmid;
     const double dist = fabs(mid - my_c) - half;
-    const bool my_far = lane < K && dist >= FF_DIST * half && dist >= my_w8;
-    const bool my_deep = my_far && dist < my_w25;
-    const unsigned long long farmask = __ballot(my_far), deepmask = __ballot(my_deep);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (my_far)
-        Sx.farlist[my_deep ? __builtin_popcountll(deepmask & below)
-                           : __builtin_popcountll(deepmask) + __builtin_popcountll(farmask & ~deepmask & below)] = lane * FARLIST_SCALE;
-    return farmask;
+    const bool my_beyond = (k < K) & (dist >= FF_DIST * half);
+    const bool my_far = my_beyond & (dist >= ((F32 && VAMP_F32_FAR_CORE) ? my_wmid : my_w8));
+    const bool my_deep = my_far & (dist < my_w25);
+    farmasks = __ballot(my_far);
+    // far list of a tile: its deep lines in line order, then the other far lines in line order.  The place of line k is
+    // the number of list members ahead of it (deep is a subset of far)
+    const unsigned far16 = ff_tile_field(farmasks, lane), deep16 = ff_tile_field(__ballot(my_deep), lane);
+    const unsigned ahead = my_deep ? (deep16 & below) : (deep16 | (far16 & below));
+    if (my_far) Sx.farlist[j][__builtin_popcount(ahead)] = (unsigned char)k;
+    widemasks = 0ull;
+    if constexpr (WIDE) {
+        const bool my_wide = ((((wide_all >> k) & 1u) != 0u) | (VAMP_MID_NODES && (my_beyond & (dist >= my_wmid)))) & !my_far;
+        widemasks = __ballot(my_wide);
+        if (my_wide) Sx.widelist[j][__builtin_popcount(ff_tile_field(widemasks, lane) & below)] = (unsigned char)k;
+    }
+    __builtin_amdgcn_wave_barrier();      // (the lists are in LDS; their readers follow in the tiles' iterations)
 }
 // node sums (lanes 0..15 hold them) -> the four local power series of the tile: lane l = 14 q + j < 56 owns
 // coefficient j of quarter q, a = sum_n M[l][n] f_n, stored in the pixel arithmetic type
@@ -864,7 +900,7 @@ __device__ __forceinline__ void ff_series(TileScratch& Sx, const double* __restr
 // (b) optical depth of the far lines at the tile's Chebyshev nodes -> the tile's local power series in Sx.coef
 //     (fp32 contexts: ff32_coefficients below, 8 nodes)
 template <class LDS>
-__device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, const double* __restrict__ dct,
+__device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, const unsigned char* farlist, const double* __restrict__ dct,
                                                 int lane, int nfar, double mid, double half, double fs_wide = 0.0) {
     const int node = lane & (FF_NODES - 1), grp = lane >> 4;
     const double tnode = dct[FF_MAT + node];                       // cos(pi (node + 1/2) / 16)
@@ -875,7 +911,8 @@ __device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, c
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int q = 4 * t + grp;
-        const LineRec& ln = *reinterpret_cast<const LineRec*>(reinterpret_cast<const char*>(L.line) + (nfar > 0 ? Sx.farlist[q < nfar ? q : nfar - 1] : 0));
+        const unsigned kf = nfar > 0 ? farlist[q < nfar ? q : nfar - 1] : 0u;
+        const LineRec& ln = *reinterpret_cast<const LineRec*>(reinterpret_cast<const char*>(L.line) + __umul24(kf, (unsigned)sizeof(LineRec)));
         Xn[t] = fabs(xnode - ln.c) * ln.s;
         yn[t] = ln.y;
         an[t] = q < nfar ? ln.amp : 0.0;
@@ -909,14 +946,14 @@ __device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, c
 // Taylor table (or the 6-level fraction beyond |z| = 8) -- and join the far lines' node sums before the one transform.
 // 16 wide lines: 4 look-ups per lane and tile instead of 64.
 template <class LDS>
-__device__ __forceinline__ double ff_wide_nodes(const LDS& L, const TileScratch& Sx, const double* __restrict__ dct, const double* tab,
+__device__ __forceinline__ double ff_wide_nodes(const LDS& L, const unsigned char* widelist, const double* __restrict__ dct, const double* tab,
                                                 int lane, int nwide, double mid, double half) {
     const int node = lane & (FF_NODES - 1), grp = lane >> 4;
     const double xnode = fma(half, dct[FF_MAT + node], mid);
     double fs = 0.0;
     for (int t = 0; 4 * t < nwide; ++t) {
         const int q = 4 * t + grp;
-        const int k = Sx.widelist[q < nwide ? q : nwide - 1];
+        const int k = widelist[q < nwide ? q : nwide - 1];
         const LineRec& ln = L.line[k];
         const double X = fabs(xnode - ln.c) * ln.s, r2 = fma(X, X, ln.y * ln.y);
         double H;
@@ -967,10 +1004,6 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
     constexpr int T = TPIX;
     static_assert(PK::LPW == 64 && PK::KCAP <= 16, "far-field tiles: one walker per wavefront, <= 16 lines");
     const int K = R.K;
-    // lane k < K classifies line k; w8 = half-width of |z|^2 < 64 around the line centre, in x units
-    // (centre and zone half-widths of "its" line are read from the record in every tile: three LDS reads
-    // instead of six registers held through the loop; the opaque index keeps the reads in the loop)
-    const int kk = lane < K ? lane : 0;
 #if VAMP_X_PREFETCH
     // the abscissae of a tile are requested one tile ahead: they head every dependency chain of the
     // tile (classification, near lines, far-field series), and an L2 round trip at the top of each of the
@@ -983,7 +1016,15 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
         xn_hi = x[base0 + 64 * T - 1];
     }
 #endif
-    for (int base = base0; base < base1; base += stride) {
+    // the lines are classified against FF_BATCH tiles at a time, at the top of every FF_BATCH-th tile (ahead of the
+    // previous batch's last tiles the pass would hold its loads in registers the loop does not have)
+    for (int batch = base0; batch < base1; batch += FF_BATCH * stride) {
+    unsigned long long farmasks, widemasks;
+    ff_classify_batch<WIDE, false>(L, Sx, x, K, lane, batch, base1, stride, (unsigned)wide_all, farmasks, widemasks);
+#pragma unroll 1
+    for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX) {
+        const int base = batch + j * stride;
+        if (base >= base1) break;
         double xi[T], tau[T];
 #if VAMP_X_PREFETCH
         const double x_lo = xn_lo, x_hi = xn_hi;
@@ -1009,31 +1050,20 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
         const double x_lo = x[base], x_hi = x[base + 64 * T - 1];
 #endif
         const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
-        int kq = kk;
-        asm volatile("" : "+v"(kq));
-        const LineRec& me = L.line[kq];
-        const unsigned long long farmask = ff_classify<(int)sizeof(LineRec)>(Sx, K, lane, me.c, me.w8, me.w25, mid, half);
-        const int nfar = __builtin_popcountll(farmask);
-        // near lines far wider than the tile join the interpolant (ff_wide_nodes); needs the lines' Taylor tables
-        unsigned long long widemask = 0ull;
-        int nwide = 0;
-        if constexpr (WIDE) {
-            widemask = wide_all & ~farmask;
-            if constexpr (VAMP_MID_NODES) {
-                // between "far" and "near": the centre is FF_DIST half-widths away, the tile still inside |z| < 8 of the line
-                // (where the node values cannot be continued fractions) but outside its Gaussian core: as smooth as a far
-                // line, evaluated at the nodes through its Taylor table like a wide one
-                const double dist = fabs(mid - me.c) - half;
-                widemask |= __ballot(lane < K && dist >= FF_DIST * half && dist >= me.wmid) & ~farmask;
-            }
-            nwide = __builtin_popcountll(widemask);
-            if ((widemask >> lane) & 1ull) Sx.widelist[__builtin_popcountll(widemask & ((1ull << lane) - 1ull))] = lane;
-        }
+        // this tile's slice of the batch: masks by scalar bit-field extraction, lists by row
+        const unsigned farmask = (unsigned)farmasks & 0xffffu;
+        const int nfar = __builtin_popcount(farmask);
+        // near lines far wider than the tile join the interpolant (ff_wide_nodes), and so do the lines between "far" and
+        // "near" (VAMP_MID_NODES): the centre is FF_DIST half-widths away, the tile still inside |z| < 8 of the line (where
+        // the node values cannot be continued fractions) but outside its Gaussian core: as smooth as a far line, evaluated
+        // at the nodes through its Taylor table like a wide one.  Needs the lines' Taylor tables
+        const unsigned widemask = WIDE ? (unsigned)widemasks & 0xffffu : 0u;
+        const int nwide = __builtin_popcount(widemask);
         // near lines: walk the set bits of the complement of the far mask (1-3 of 16 on the headline)
         // (VAMP_SKIP_*: timing-only builds of tools/variants.py -- the phase split in profiles/)
 #ifndef VAMP_SKIP_NEAR
-        for (unsigned long long near = ~(farmask | widemask) & ((1ull << K) - 1ull); near; near &= near - 1ull) {
-            const int k = __builtin_ctzll(near);
+        for (unsigned near = ~(farmask | widemask) & ((1u << K) - 1u); near; near &= near - 1u) {
+            const int k = __builtin_ctz(near);
             const LineRec ln = L.line[k];
             double X[T], H[T];
 #pragma unroll
@@ -1052,11 +1082,10 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             double fs_wide = 0.0;
             if constexpr (WIDE) {
                 if (nwide > 0) {
-                    __builtin_amdgcn_wave_barrier();          // (the wide list is in LDS)
-                    fs_wide = ff_wide_nodes<typename PK::Lds>(L, Sx, dct, tab, lane, nwide, mid, half);
+                    fs_wide = ff_wide_nodes<typename PK::Lds>(L, Sx.widelist[j], dct, tab, lane, nwide, mid, half);
                 }
             }
-            ff_coefficients<typename PK::Lds>(L, Sx, dct, lane, nfar, mid, half, fs_wide);
+            ff_coefficients<typename PK::Lds>(L, Sx, Sx.farlist[j], dct, lane, nfar, mid, half, fs_wide);
         }
 #endif
 #if VAMP_EARLY_LOADS
@@ -1089,6 +1118,7 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             const double r = (fi[t] - m) * wi[t];
             chi = fma(r, r, chi);
         }
+    }
     }
 }
 
@@ -1210,8 +1240,8 @@ __device__ __forceinline__ void sweep_range_f32(const RegionDev& R, const typena
 // shuffles, a 32 x 8 float matrix (row sums <= 3.4: no conditioning problem in fp32) -> four local series of 8
 // coefficients, 7 multiply-adds per pixel.  Node values through W4 regions I / II (every far point has |z| >= 8).
 template <class LDS>
-__device__ __forceinline__ void ff32_coefficients(const LDS& L, TileScratch& Sx, const float* __restrict__ dct32, int lane, int nfar,
-                                                  double mid, double half) {
+__device__ __forceinline__ void ff32_coefficients(const LDS& L, TileScratch& Sx, const unsigned char* farlist, const float* __restrict__ dct32,
+                                                  int lane, int nfar, double mid, double half) {
     const int node = lane & (FF32_NODES - 1), grp = lane >> 3;
     const float tnode = dct32[FF32_MAT + node];                    // cos(pi (node + 1/2) / 8)
     __builtin_amdgcn_wave_barrier();
@@ -1220,7 +1250,7 @@ __device__ __forceinline__ void ff32_coefficients(const LDS& L, TileScratch& Sx,
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int q = 8 * t + grp;
-        const float* lf = reinterpret_cast<const float*>(reinterpret_cast<const char*>(L.linef) + Sx.farlist[q < nfar ? q : nfar - 1]);
+        const float* lf = L.linef[farlist[q < nfar ? q : nfar - 1]];
         X[t] = fabsf(xn - lf[0]) * lf[1];
         yv[t] = lf[2];
         av[t] = q < nfar ? lf[3] : 0.0f;
@@ -1289,8 +1319,15 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
     constexpr int T = TPIX;
     static_assert(PK::LPW == 64 && PK::KCAP <= 16 && MODE != VAMP_GAUSS3, "far-field tiles: one walker per wavefront, Voigt lines");
     const int K = R.K;
-    const int kk = lane < K ? lane : 0;
-    for (int base = base0; base < base1; base += stride) {
+    for (int batch = base0; batch < base1; batch += FF_BATCH * stride) {
+    // (fp32: the node values are W4 regions I / II, valid from |x| + y = 5.5 -- no |z| >= 8 condition as for the fp64
+    //  fractions: a line is far once the tile is outside its Gaussian core, |z|^2 >= VAMP_MID_Z2)
+    unsigned long long farmasks, widemasks;
+    ff_classify_batch<false, true>(L, Sx, x, K, lane, batch, base1, stride, 0u, farmasks, widemasks);
+#pragma unroll 1
+    for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX) {
+        const int base = batch + j * stride;
+        if (base >= base1) break;
         float xi[T], tau[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
@@ -1299,17 +1336,12 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
         }
         const double x_lo = (double)x[base], x_hi = (double)x[base + 64 * T - 1];
         const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
-        int kq = kk;
-        asm volatile("" : "+v"(kq));
-        const LineRec& me = L.line[kq];
-        // (fp32: the node values are W4 regions I / II, valid from |x| + y = 5.5 -- no |z| >= 8 condition as for the fp64
-        //  fractions: a line is far once the tile is outside its Gaussian core, |z|^2 >= VAMP_MID_Z2)
-        const unsigned long long farmask = ff_classify<4 * (int)sizeof(float)>(Sx, K, lane, me.c, VAMP_F32_FAR_CORE ? me.wmid : me.w8, me.w25, mid, half);
-        const int nfar = __builtin_popcountll(farmask);
+        const unsigned farmask = (unsigned)farmasks & 0xffffu;
+        const int nfar = __builtin_popcount(farmask);
         // (VAMP_SKIP_*: timing-only builds of tools/variants.py -- the phase split in profiles/)
 #ifndef VAMP_SKIP_NEAR
-        for (unsigned long long near = ~farmask & ((1ull << K) - 1ull); near; near &= near - 1ull) {
-            const int k = __builtin_ctzll(near);
+        for (unsigned near = ~farmask & ((1u << K) - 1u); near; near &= near - 1u) {
+            const int k = __builtin_ctz(near);
             const float c = L.linef[k][0], sc = L.linef[k][1], y = L.linef[k][2], a = L.linef[k][3];
             float X[T], H[T];
 #pragma unroll
@@ -1322,7 +1354,7 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
 #endif
         if (nfar > 0) {
 #ifndef VAMP_SKIP_FFNODES
-            ff32_coefficients<typename PK::Lds>(L, Sx, reinterpret_cast<const float*>(dct), lane, nfar, mid, half);
+            ff32_coefficients<typename PK::Lds>(L, Sx, Sx.farlist[j], reinterpret_cast<const float*>(dct), lane, nfar, mid, half);
 #endif
 #ifndef VAMP_SKIP_CLENSHAW
             ff32_horner<T>(Sx, xi, mid, half, x_hi > x_lo, tau);
@@ -1339,6 +1371,7 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
             const float r = (f[i] - m) * wt[i];
             chi += (double)r * (double)r;
         }
+    }
     }
 }
 
