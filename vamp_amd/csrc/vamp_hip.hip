@@ -358,12 +358,26 @@ __device__ __forceinline__ double uniform_logp(double v, double lo, double hi, d
     return (v >= lo && v <= hi) ? lp : NEG_INF;
 }
 
+// The two rare cases of the far-field node evaluation (ff_eval2) are decided by a walker's lines, not by the tile:
+//   tiny:  y < Y_TINY -- the fractions miss e^{-x^2}, which ff_eval2 adds back;
+//   reach: the line is so narrow that a node of the region can lie beyond X_FAR in its z, where ff_eval2 clamps the
+//          argument and patches the value.  Every node lies between the region's first and last abscissa (the grid is
+//          monotonic, vamp_set_regions checks it), |x - c| is largest at one of the two ends wherever c lies, and rounding
+//          is monotonic, so s max(|x_first - c|, |x_last - c|) bounds every node's X as computed; NaN sets the bit.
+// One line with either bit sends its walker through the guarded copy of the tile loop -- today's code -- and a walker
+// without runs the copy that has neither the clamps nor the votes (sweep_class).
+__device__ __forceinline__ void ff_guard_bits(const LineRec& rec, double x_first, double x_last, bool& tiny, bool& reach) {
+    tiny = !(rec.y >= vamp::Y_TINY);
+    reach = !(rec.s * fmax(fabs(x_first - rec.c), fabs(x_last - rec.c)) <= vamp::X_FAR);
+}
+
 // Turn theta (in LDS) into line records + prior.  Returns log-prior on every lane.
 // MODE is a compile-time parameter: one specialised kernel per parameterisation, no mode
 // branches in the staging code or in the pixel loop.
-template <int MODE, class PK = PackWide, bool TAB = false, bool TAB32 = false, bool DT32 = false>
+// FFG (ff_guard_bits): the walker's two guard bits of the fp64 far-field node evaluation, from the region's abscissae xr.
+template <int MODE, class PK = PackWide, bool TAB = false, bool TAB32 = false, bool DT32 = false, bool FFG = false>
 __device__ __forceinline__ double stage_lines(const RegionDev& R, typename PK::Lds& L, int lane, bool want_f32, int part,
-                                              double* tab = nullptr) {
+                                              double* tab = nullptr, const double* __restrict__ xr = nullptr) {
     // `lane` is the lane index inside the walker's group (0 .. LPW-1).  In a split workgroup
     // (`part` = wavefront index) the FIRST wavefront evaluates the records and the prior and leaves the
     // prior in a spare slot of the parameter block for the others (each needs it to decide whether to
@@ -372,8 +386,9 @@ __device__ __forceinline__ double stage_lines(const RegionDev& R, typename PK::L
     // line -- was 3 % of its instructions three times over.)
     const bool writer = !PK::SPLIT || part == 0;
     constexpr int LP_SLOT = 4 * PK::KCAP + 3;       // theta holds at most 4 KCAP + 1 parameters
-    constexpr int WIDE_SLOT = 4 * PK::KCAP + 2;     // far-field shapes: bit k set = line k is far wider than a tile (ff_wide_nodes)
-    bool my_wide = false;
+    constexpr int WIDE_SLOT = 4 * PK::KCAP + 2;     // far-field shapes: bit k set = line k is far wider than a tile (ff_wide_nodes);
+                                                    // bits 16, 17: the guard bits
+    bool my_wide = false, my_tiny = false, my_reach = false;
     double lp = 0.0;
     const int K = R.K;
     constexpr int Q = (MODE == VAMP_VOIGT4) ? 4 : 3;
@@ -421,6 +436,7 @@ __device__ __forceinline__ double stage_lines(const RegionDev& R, typename PK::L
                 rec.wmid = sqrt(fmax(VAMP_MID_Z2 - rec.y * rec.y, 0.0)) / rec.s;
                 // half of the region's widest tile is at most VAMP_WIDE_MAX in this line's z: smooth across every tile
                 my_wide = VAMP_WIDE_NODES && TAB && rec.s * (0.5 * R.tile_span) <= VAMP_WIDE_MAX;
+                if constexpr (FFG) ff_guard_bits(rec, xr[0], xr[R.P - 1], my_tiny, my_reach);
             } else {
                 rec.w8 = rec.w25 = rec.wmid = 0.0;
             }
@@ -435,8 +451,9 @@ __device__ __forceinline__ double stage_lines(const RegionDev& R, typename PK::L
             L.linef[lane][3] = (float)(MODE == VAMP_GAUSS3 ? rec.amp : rec.amp * SQRT_PI);   // W4 returns H itself
         }
     }
-    if constexpr (PK::FF && TAB && VAMP_WIDE_NODES) {
-        const unsigned long long wm = __ballot(my_wide);
+    if constexpr (PK::FF && ((TAB && VAMP_WIDE_NODES) || FFG)) {
+        unsigned long long wm = __ballot(my_wide);
+        if constexpr (FFG) wm |= (__ballot(my_tiny) ? 1ull << 16 : 0ull) | (__ballot(my_reach) ? 1ull << 17 : 0ull);
         if (writer && lane == 0) L.theta[WIDE_SLOT] = __longlong_as_double((long long)wm);
     }
     if (R.sample_sd && lane == PK::KCAP && writer) {      // one otherwise idle lane: sd ~ U(0,1), vpfits.py:39
@@ -795,14 +812,18 @@ __device__ __forceinline__ void ff_frac2(const double (&X)[2], const double (&y)
     H[1] = n[1] * (ra * d[0]);
 }
 
+// GUARD = false: staging has established for this walker (ff_guard_bits) that no line reaches X > X_FAR at a node of the
+// region and none has y < Y_TINY -- the clamp is the identity and neither patch can fire, so they are not compiled: the
+// same bits from about six vector instructions fewer per call.
+template <bool GUARD = true>
 __device__ __forceinline__ void ff_eval2(const double (&Xin)[2], const double (&y)[2], double (&H)[2], const double* ec) {
     double X[2], r2[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        X[t] = fmin(Xin[t], vamp::X_FAR);       // lanes hold different lines: always guard the promotion
+        X[t] = GUARD ? fmin(Xin[t], vamp::X_FAR) : Xin[t];       // lanes hold different lines: guard the promotion
         r2[t] = fma(X[t], X[t], y[t] * y[t]);
     }
-    const double lo = fmin(r2[0], r2[1]), hi = fmax(Xin[0], Xin[1]), ymin = fmin(y[0], y[1]);
+    const double lo = fmin(r2[0], r2[1]);
     // the fractions' ranges for NODE values: 4e-13 / 2e-13 / 9e-13 of the value at the lower ends (the m-level fraction is
     // the 2m-point Gauss-Hermite rule of w's integral; the pixel evaluator's own ranges, R2_M4 / M3 / M2 = 196 / 625 / 1e4,
     // hold 2e-15) -- the series these values feed reproduce a wing to 3e-11 of its value
@@ -815,6 +836,8 @@ __device__ __forceinline__ void ff_eval2(const double (&Xin)[2], const double (&
     } else {
         ff_frac2<2>(X, y, r2, H);               // valid (more than accurate) beyond 1e8 too, up to X_FAR
     }
+    if constexpr (!GUARD) return;
+    const double hi = fmax(Xin[0], Xin[1]), ymin = fmin(y[0], y[1]);
     if (__any(hi > vamp::X_FAR)) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -841,8 +864,8 @@ __device__ __forceinline__ unsigned ff_tile_field(unsigned long long batchmask, 
     const unsigned h = (lane & 32) ? (unsigned)(batchmask >> 32) : (unsigned)batchmask;
     return (h >> (lane & 16)) & 0xffffu;
 }
-template <bool WIDE, bool F32, class LDS, class xreal>
-__device__ __forceinline__ void ff_classify_batch(const LDS& L, TileScratch& Sx, const xreal* __restrict__ x, int K, int lane_, int base,
+template <bool WIDE, bool F32, class LDS>
+__device__ __forceinline__ void ff_classify_batch(const LDS& L, TileScratch& Sx, const double2* __restrict__ geo, int K, int lane_, int base,
                                                   int base1, int stride, unsigned wide_all,
                                                   unsigned long long& farmasks, unsigned long long& widemasks) {
     // everything a lane derives from its index is derived here, once per batch, from an opaque copy: hoisted out of
@@ -853,8 +876,8 @@ __device__ __forceinline__ void ff_classify_batch(const LDS& L, TileScratch& Sx,
     const unsigned below = (1u << k) - 1u;
     int bj = base + j * stride;
     bj = bj < base1 ? bj : base;
-    const double x_lo = (double)x[bj], x_hi = (double)x[bj + 64 * TPIX - 1];
-    const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
+    const double2 g = geo[bj >> 8];       // (mid, half) of "its" tile: one load instead of two abscissae and their arithmetic
+    const double mid = g.x, half = fabs(g.y);
     // centre and zone half-widths of "its" line: four LDS reads per batch, all issued together (no short-circuit
     // evaluation below: the predicates are bit operations on compare results, the pass has no branches but the writes)
     const LineRec& me = *reinterpret_cast<const LineRec*>(reinterpret_cast<const char*>(L.line) +
@@ -899,7 +922,7 @@ __device__ __forceinline__ void ff_series(TileScratch& Sx, const double* __restr
 }
 // (b) optical depth of the far lines at the tile's Chebyshev nodes -> the tile's local power series in Sx.coef
 //     (fp32 contexts: ff32_coefficients below, 8 nodes)
-template <class LDS>
+template <class LDS, bool GUARD = true>
 __device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, const unsigned char* farlist, const double* __restrict__ dct,
                                                 int lane, int nfar, double mid, double half, double fs_wide = 0.0) {
     const int node = lane & (FF_NODES - 1), grp = lane >> 4;
@@ -921,13 +944,13 @@ __device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, c
     if (nfar > 0) {
         const double Xa[2] = {Xn[0], Xn[1]}, ya[2] = {yn[0], yn[1]};
         double Ha[2];
-        ff_eval2(Xa, ya, Ha, dct + FF_EXP);
+        ff_eval2<GUARD>(Xa, ya, Ha, dct + FF_EXP);
         fs = fma(an[0], Ha[0], an[1] * Ha[1]);
     }
     if (nfar > 8) {                               // list entries 8..15 (slots 2, 3)
         const double Xb[2] = {Xn[2], Xn[3]}, yb[2] = {yn[2], yn[3]};
         double Hb[2];
-        ff_eval2(Xb, yb, Hb, dct + FF_EXP);
+        ff_eval2<GUARD>(Xb, yb, Hb, dct + FF_EXP);
         fs += fma(an[2], Hb[0], an[3] * Hb[1]);
     }
     fs += fs_wide;
@@ -969,18 +992,16 @@ __device__ __forceinline__ double ff_wide_nodes(const LDS& L, const unsigned cha
 }
 // (c) Horner's rule at the tile's pixels, added to tau (in the pixel arithmetic type).  Register t of a
 //     lane is pixel 64 t + lane of the tile: quarter t of an ascending grid, 3 - t of a descending one.
+//     u[t]: the pixel's place in its quarter, from the context's table (k_tile_tables).  `up`: the grid ascends.
 template <class real, int T>
-__device__ __forceinline__ void ff_horner(const TileScratch& Sx, const real (&xi)[T], double mid, double half, bool up,
-                                          real (&tau)[T]) {
+__device__ __forceinline__ void ff_horner(const TileScratch& Sx, const real (&u)[T], bool up, real (&tau)[T]) {
     static_assert(T == 4, "one pixel per quarter of the tile");
-    const real scale = (real)(4.0 * vamp::rcp_nr(half));     // (a last-bit error in the scale moves u by 1e-16)
-    real u[T], acc[T];
+    real acc[T];
     const real* cq[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int q = up ? t : T - 1 - t;
         cq[t] = reinterpret_cast<const real*>(Sx.coef) + q * (FF_DEG + 1);
-        u[t] = (xi[t] - (real)fma(half, 0.5 * q - 0.75, mid)) * scale;
         acc[t] = cq[t][FF_DEG];
     }
 #pragma unroll
@@ -996,10 +1017,14 @@ __device__ __forceinline__ void ff_horner(const TileScratch& Sx, const real (&xi
 // WIDE: this walker has lines far wider than a tile (ff_wide_nodes).  A copy of the loop of its own, chosen per walker
 // by a wave-uniform branch: compiled into the one loop, the wide path cost the converged headline ensemble -- which has no
 // such line -- 2.8 % through the loop's register allocation (profiles/r04_e_wide_lines.txt).
-template <int MODE, class PK, bool TAB, bool WIDE = false>
+// GUARD: some line of this walker needs ff_eval2's clamp or one of its patches (ff_guard_bits); chosen the same way.
+// The tile's geometry comes from the context's tables (k_tile_tables): (mid, half) of tile `base` in geo[base >> 8], one
+// 16-byte load at a wave-uniform address; the pixels' places in their quarters in ut[], requested after the near lines.
+template <int MODE, class PK, bool TAB, bool WIDE = false, bool GUARD = true>
 __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typename PK::Lds& L, TileScratch& Sx, const double* __restrict__ dct,
                                                const double* __restrict__ x, const double* __restrict__ f,
-                                               const double* __restrict__ wt, int lane, int base0, int base1, int stride,
+                                               const double* __restrict__ wt, const double* __restrict__ ut,
+                                               const double2* __restrict__ geo, int lane, int base0, int base1, int stride,
                                                double& chi, const double* tab, unsigned long long wide_all = 0ull) {
     constexpr int T = TPIX;
     static_assert(PK::LPW == 64 && PK::KCAP <= 16, "far-field tiles: one walker per wavefront, <= 16 lines");
@@ -1008,26 +1033,23 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
     // the abscissae of a tile are requested one tile ahead: they head every dependency chain of the
     // tile (classification, near lines, far-field series), and an L2 round trip at the top of each of the
     // 16 iterations is paid by all the wavefronts of a workgroup together
-    double xn[T], xn_lo = 0.0, xn_hi = 0.0;
+    double xn[T];
     if (base0 < base1) {
 #pragma unroll
         for (int t = 0; t < T; ++t) xn[t] = x[base0 + 64 * t + lane];
-        xn_lo = x[base0];
-        xn_hi = x[base0 + 64 * T - 1];
     }
 #endif
     // the lines are classified against FF_BATCH tiles at a time, at the top of every FF_BATCH-th tile (ahead of the
     // previous batch's last tiles the pass would hold its loads in registers the loop does not have)
     for (int batch = base0; batch < base1; batch += FF_BATCH * stride) {
     unsigned long long farmasks, widemasks;
-    ff_classify_batch<WIDE, false>(L, Sx, x, K, lane, batch, base1, stride, (unsigned)wide_all, farmasks, widemasks);
+    ff_classify_batch<WIDE, false>(L, Sx, geo, K, lane, batch, base1, stride, (unsigned)wide_all, farmasks, widemasks);
 #pragma unroll 1
     for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX) {
         const int base = batch + j * stride;
         if (base >= base1) break;
         double xi[T], tau[T];
 #if VAMP_X_PREFETCH
-        const double x_lo = xn_lo, x_hi = xn_hi;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             xi[t] = xn[t];
@@ -1037,8 +1059,6 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             const int nb = base + stride < base1 ? base + stride : base;     // the last tile re-reads itself
 #pragma unroll
             for (int t = 0; t < T; ++t) xn[t] = x[nb + 64 * t + lane];
-            xn_lo = x[nb];
-            xn_hi = x[nb + 64 * T - 1];
         }
 #else
 #pragma unroll
@@ -1046,10 +1066,11 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             xi[t] = x[base + 64 * t + lane];
             tau[t] = 0.0;
         }
-        // tile geometry (wave-uniform)
-        const double x_lo = x[base], x_hi = x[base + 64 * T - 1];
 #endif
-        const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
+        // tile geometry (wave-uniform): the table's half carries the grid's orientation in its sign
+        const double2 tg = geo[base >> 8];
+        const double mid = tg.x, half = fabs(tg.y);
+        const bool up = __double2hiint(tg.y) >= 0;
         // this tile's slice of the batch: masks by scalar bit-field extraction, lists by row
         const unsigned farmask = (unsigned)farmasks & 0xffffu;
         const int nfar = __builtin_popcount(farmask);
@@ -1077,28 +1098,43 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
         // exponentials that separate them from their use: left to itself the compiler sinks each
         // load to its use and the wavefront sits through eight L2 round trips per tile
         double fi[T], wi[T];
-#ifndef VAMP_SKIP_FFNODES
         if (nfar + nwide > 0) {
+            // the pixels' places in their quarters, requested ahead of the node stage that hides the round trip: xi has
+            // ended with the near lines, u takes its registers.  (One block from here to Horner's rule: requested in a
+            // block of their own the loads are sunk to their use, behind the node stage.)
+            double u[T];
+#pragma unroll
+            for (int t = 0; t < T; ++t) u[t] = ut[base + 64 * t + lane];
+#ifndef VAMP_SKIP_FFNODES
             double fs_wide = 0.0;
             if constexpr (WIDE) {
                 if (nwide > 0) {
                     fs_wide = ff_wide_nodes<typename PK::Lds>(L, Sx.widelist[j], dct, tab, lane, nwide, mid, half);
                 }
             }
-            ff_coefficients<typename PK::Lds>(L, Sx, Sx.farlist[j], dct, lane, nfar, mid, half, fs_wide);
-        }
+            ff_coefficients<typename PK::Lds, GUARD>(L, Sx, Sx.farlist[j], dct, lane, nfar, mid, half, fs_wide);
 #endif
 #if VAMP_EARLY_LOADS
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            fi[t] = f[base + 64 * t + lane];
-            wi[t] = wt[base + 64 * t + lane];
-        }
-        __builtin_amdgcn_sched_barrier(0);
+            for (int t = 0; t < T; ++t) {
+                fi[t] = f[base + 64 * t + lane];
+                wi[t] = wt[base + 64 * t + lane];
+            }
+            __builtin_amdgcn_sched_barrier(0);
 #endif
 #ifndef VAMP_SKIP_CLENSHAW
-        if (nfar + nwide > 0) ff_horner<double, T>(Sx, xi, mid, half, x_hi > x_lo, tau);
+            ff_horner<double, T>(Sx, u, up, tau);
 #endif
+        } else {
+#if VAMP_EARLY_LOADS
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                fi[t] = f[base + 64 * t + lane];
+                wi[t] = wt[base + 64 * t + lane];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
         // the exp constants are read from LDS here, per tile: as literals they sit in ~30 SGPRs (or VGPRs) through
         // the whole loop, and the pointers and masks they displace are then reloaded from VGPR lanes in every tile
         int eoff = FF_EXP;
@@ -1284,18 +1320,14 @@ __device__ __forceinline__ void ff32_coefficients(const LDS& L, TileScratch& Sx,
 }
 // Horner's rule at the tile's pixels (register t of a lane = pixel 64 t + lane: quarter t of an ascending grid)
 template <int T>
-__device__ __forceinline__ void ff32_horner(const TileScratch& Sx, const float (&xi)[T], double mid, double half, bool up,
-                                            float (&tau)[T]) {
+__device__ __forceinline__ void ff32_horner(const TileScratch& Sx, const float (&u)[T], bool up, float (&tau)[T]) {
     static_assert(T == 4, "one pixel per quarter of the tile");
-    const float hf = (float)half, mf = (float)mid;
-    const float scale = 4.0f * __builtin_amdgcn_rcpf(hf);
-    float u[T], acc[T];
+    float acc[T];
     const float* cq[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int q = up ? t : T - 1 - t;
         cq[t] = reinterpret_cast<const float*>(Sx.coef) + q * (FF32_DEG + 1);
-        u[t] = (xi[t] - fmaf(hf, 0.5f * q - 0.75f, mf)) * scale;
         acc[t] = cq[t][FF32_DEG];
     }
 #pragma unroll
@@ -1314,7 +1346,8 @@ __device__ __forceinline__ void ff32_horner(const TileScratch& Sx, const float (
 template <int MODE, class PK, bool TAB32>
 __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typename PK::Lds& L, TileScratch& Sx,
                                                    const double* __restrict__ dct, const float* __restrict__ x,
-                                                   const float* __restrict__ f, const float* __restrict__ wt, int lane,
+                                                   const float* __restrict__ f, const float* __restrict__ wt,
+                                                   const float* __restrict__ ut, const double2* __restrict__ geo, int lane,
                                                    int base0, int base1, int stride, double& chi, const float* tab32) {
     constexpr int T = TPIX;
     static_assert(PK::LPW == 64 && PK::KCAP <= 16 && MODE != VAMP_GAUSS3, "far-field tiles: one walker per wavefront, Voigt lines");
@@ -1323,7 +1356,7 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
     // (fp32: the node values are W4 regions I / II, valid from |x| + y = 5.5 -- no |z| >= 8 condition as for the fp64
     //  fractions: a line is far once the tile is outside its Gaussian core, |z|^2 >= VAMP_MID_Z2)
     unsigned long long farmasks, widemasks;
-    ff_classify_batch<false, true>(L, Sx, x, K, lane, batch, base1, stride, 0u, farmasks, widemasks);
+    ff_classify_batch<false, true>(L, Sx, geo, K, lane, batch, base1, stride, 0u, farmasks, widemasks);
 #pragma unroll 1
     for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX) {
         const int base = batch + j * stride;
@@ -1334,8 +1367,9 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
             xi[t] = x[base + 64 * t + lane];
             tau[t] = 0.0f;
         }
-        const double x_lo = (double)x[base], x_hi = (double)x[base + 64 * T - 1];
-        const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
+        const double2 tg = geo[base >> 8];        // (as in sweep_range_ff)
+        const double mid = tg.x, half = fabs(tg.y);
+        const bool up = __double2hiint(tg.y) >= 0;
         const unsigned farmask = (unsigned)farmasks & 0xffffu;
         const int nfar = __builtin_popcount(farmask);
         // (VAMP_SKIP_*: timing-only builds of tools/variants.py -- the phase split in profiles/)
@@ -1353,11 +1387,14 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
         }
 #endif
         if (nfar > 0) {
+            float u[T];             // requested ahead of the node stage that hides the round trip
+#pragma unroll
+            for (int t = 0; t < T; ++t) u[t] = ut[base + 64 * t + lane];
 #ifndef VAMP_SKIP_FFNODES
             ff32_coefficients<typename PK::Lds>(L, Sx, Sx.farlist[j], reinterpret_cast<const float*>(dct), lane, nfar, mid, half);
 #endif
 #ifndef VAMP_SKIP_CLENSHAW
-            ff32_horner<T>(Sx, xi, mid, half, x_hi > x_lo, tau);
+            ff32_horner<T>(Sx, u, up, tau);
 #endif
         }
 #pragma unroll
@@ -1378,7 +1415,46 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
 struct PixPtrs {
     const double* x; const double* f; const double* wt;       // fp64 copies
     const float* xf; const float* ff; const float* wtf;       // fp32 copies (may be null)
+    // far-field tables of the full tiles (k_tile_tables; null when no region has one): the pixels' places in their
+    // quarters, indexed like x (fp64 contexts: u, fp32 contexts: uf), and (mid, +-half) of the tile that starts at
+    // global pixel g in geo[g >> 8]
+    const double* u; const float* uf; const double2* geo;
 };
+
+// The far-field tables of a context, built once per vamp_set_regions: what the tile loop used to recompute for every
+// (walker, tile) though it depends on the region's abscissae alone.  Workgroup (tile, region), one thread per pixel.
+//   geo[(pix_off + base) >> 8] = (mid, +-half) of the full tile at `base` -- a region's full tiles never share a slot with
+//       another region's, whatever pix_off -- with the grid's orientation in the sign of half (+: ascending);
+//   u[pix_off + i] (fp32 contexts: uf) = the pixel's place in its quarter of the tile, in the arithmetic ff_horner /
+//       ff32_horner had for it (same device functions: a hardware reciprocal has no host twin); 0 past the last full tile.
+template <bool F32>
+__global__ __launch_bounds__(64 * TPIX) void k_tile_tables(const RegionDev* __restrict__ regions, const double* __restrict__ x,
+                                                           const float* __restrict__ xf, double* __restrict__ u, float* __restrict__ uf,
+                                                           double2* __restrict__ geo) {
+    const RegionDev& R = regions[blockIdx.y];
+    const int base = (int)blockIdx.x * (64 * TPIX), i = base + (int)threadIdx.x;
+    if (i >= R.P) return;
+    const long long g = R.pix_off + i;
+    if (base + 64 * TPIX > R.P) {           // the tail: never read through the tables
+        if constexpr (F32) uf[g] = 0.0f;
+        else u[g] = 0.0;
+        return;
+    }
+    const long long g0 = R.pix_off + base, g1 = g0 + 64 * TPIX - 1;
+    const double x_lo = F32 ? (double)xf[g0] : x[g0], x_hi = F32 ? (double)xf[g1] : x[g1];
+    const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
+    const bool up = x_hi > x_lo;
+    const int t = (int)threadIdx.x >> 6, q = up ? t : TPIX - 1 - t;
+    if constexpr (F32) {
+        const float hf = (float)half, mf = (float)mid;
+        const float scale = 4.0f * __builtin_amdgcn_rcpf(hf);
+        uf[g] = (xf[g] - fmaf(hf, 0.5f * q - 0.75f, mf)) * scale;
+    } else {
+        const double scale = 4.0 * vamp::rcp_nr(half);     // (a last-bit error in the scale moves u by 1e-16)
+        u[g] = (x[g] - fma(half, 0.5 * q - 0.75, mid)) * scale;
+    }
+    if (threadIdx.x == 0) geo[g0 >> 8] = make_double2(mid, up ? half : -half);
+}
 
 // Sum over the walker's pixels of ((f - m) w)^2, on every lane.  One walker per wavefront (LPW = 64):
 // full tiles are dealt round-robin into PARTS classes, each class is summed over its tiles and
@@ -1393,8 +1469,8 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
     if constexpr (F32) {
         const float* x = px.xf + R.pix_off; const float* f = px.ff + R.pix_off; const float* wt = px.wtf + R.pix_off;
         if constexpr (VAMP_FARFIELD && PK::FF && MODE != VAMP_GAUSS3 && TPIX == 4)
-            sweep_range_f32_ff<MODE, PK, use_tables32<F32, MODE, PK>()>(R, L, Sx, dct, x, f, wt, lane, base0, full, stride, chi,
-                                                                        reinterpret_cast<const float*>(tab));
+            sweep_range_f32_ff<MODE, PK, use_tables32<F32, MODE, PK>()>(R, L, Sx, dct, x, f, wt, px.uf + R.pix_off, px.geo + (R.pix_off >> 8),
+                                                                        lane, base0, full, stride, chi, reinterpret_cast<const float*>(tab));
         else if (TPIX > 1) sweep_range_f32<MODE, PK, TPIX>(R, L, x, f, wt, lane, base0, full, stride, chi);
         if constexpr (PK::TAIL || TPIX == 1)
             if (tail) {
@@ -1415,14 +1491,25 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
     } else {
         const double* x = px.x + R.pix_off; const double* f = px.f + R.pix_off; const double* wt = px.wt + R.pix_off;
         if constexpr (VAMP_FARFIELD && PK::FF && MODE != VAMP_GAUSS3 && TPIX == 4) {
+            // a tile starts at a multiple of 256 pixels of its region, so tile `base` is slot (pix_off >> 8) + (base >> 8)
+            const double* ut = px.u + R.pix_off;
+            const double2* geo = px.geo + (R.pix_off >> 8);
+            // what stage_lines left in the parameter block: the mask of the lines far wider than a tile (none on a
+            // converged ensemble) and, above it, the walker's guard bits (ff_guard_bits)
+            const int flags = __builtin_amdgcn_readfirstlane((int)(__double_as_longlong(L.theta[4 * PK::KCAP + 2]) & 0x3ffff));
+            const bool guard = (flags >> 16) != 0;
             if constexpr (VAMP_WIDE_NODES && TAB) {
-                // lines far wider than a tile (stage_lines left their mask in the parameter block): none on a converged ensemble
-                const unsigned long long wide_all =
-                    (unsigned long long)__builtin_amdgcn_readfirstlane((int)(__double_as_longlong(L.theta[4 * PK::KCAP + 2]) & 0xffff));
-                if (VAMP_MID_NODES || wide_all) sweep_range_ff<MODE, PK, TAB, true>(R, L, Sx, dct, x, f, wt, lane, base0, full, stride, chi, tab, wide_all);
-                else sweep_range_ff<MODE, PK, TAB, false>(R, L, Sx, dct, x, f, wt, lane, base0, full, stride, chi, tab);
+                const unsigned long long wide_all = (unsigned long long)(flags & 0xffff);
+                if (VAMP_MID_NODES || wide_all) {
+                    if (guard) sweep_range_ff<MODE, PK, TAB, true, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all);
+                    else sweep_range_ff<MODE, PK, TAB, true, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all);
+                } else {
+                    if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
+                    else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
+                }
             } else {
-                sweep_range_ff<MODE, PK, TAB>(R, L, Sx, dct, x, f, wt, lane, base0, full, stride, chi, tab);
+                if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
+                else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
             }
         } else if (TPIX > 1) sweep_range<MODE, PK, TPIX, TAB>(R, L, x, f, wt, lane, base0, full, stride, chi, tab);
         if constexpr (PK::TAIL || TPIX == 1)
@@ -1642,8 +1729,9 @@ __device__ __forceinline__ double loglike_from_sum(const RegionDev& R, const LDS
 template <bool F32, int MODE, class PK = PackWide>
 __device__ __forceinline__ double wave_lnprob(const RegionDev& R, typename PK::Lds& L, TileScratch& Sx, const double* dct,
                                               const PixPtrs& px, int lane, double* chi_out, int part, double* red, double* tab) {
+    constexpr bool FFG = VAMP_FARFIELD && PK::FF && !F32 && MODE != VAMP_GAUSS3 && pixels_per_lane<PK>() == 4;   // sweep_class reads the bits
     const double lp = stage_lines<MODE, PK, use_tables<F32, MODE, PK>() && PK::LINES_PER_PASS == 0, use_tables32<F32, MODE, PK>(),
-                                  use_blend32<F32, MODE, PK>()>(R, L, lane, F32, part, tab);
+                                  use_blend32<F32, MODE, PK>(), FFG>(R, L, lane, F32, part, tab, FFG ? px.x + R.pix_off : nullptr);
     VAMP_STAMP(3);
     if (!(lp > NEG_INF) || lp != lp) {       // outside the prior (or NaN): skip the sweep
         if (chi_out) *chi_out = __builtin_nan("");
@@ -2498,7 +2586,15 @@ struct vamp_ctx : vamp::AbiState {
     bool timing = false;
     EventPairs ktiming;
 
-    PixPtrs pix() const { return PixPtrs{x_d.get(), f_d.get(), wt_d.get(), xf_d.get(), ff_d.get(), wtf_d.get()}; }
+    // far-field tables of the regions' full tiles (k_tile_tables, launched by vamp_set_regions): one real per pixel and
+    // two doubles per 256 pixels; empty when no region has a full tile the far-field sweep could run on
+    DevBuf<double> u_d;
+    DevBuf<float> uf_d;
+    DevBuf<double2> geo_d;
+
+    PixPtrs pix() const {
+        return PixPtrs{x_d.get(), f_d.get(), wt_d.get(), xf_d.get(), ff_d.get(), wtf_d.get(), u_d.get(), uf_d.get(), geo_d.get()};
+    }
 };
 
 namespace {
@@ -2508,6 +2604,7 @@ void reset_regions(vamp_ctx* c) {
     c->regions_d.reset();
     c->x_d.reset(); c->f_d.reset(); c->wt_d.reset();
     c->xf_d.reset(); c->ff_d.reset(); c->wtf_d.reset();
+    c->u_d.reset(); c->uf_d.reset(); c->geo_d.reset();
     c->classes.clear();
     c->classes_small.clear();
     c->n_regions = 0;
@@ -3203,6 +3300,23 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
     }
     HIP_TRY(c->regions_d.ensure(n_regions));
     HIP_TRY(hipMemcpy(c->regions_d.get(), R.data(), n_regions * sizeof(RegionDev), hipMemcpyHostToDevice));
+    // far-field tables (k_tile_tables), where a sweep can read them: Voigt lines and some region with a full tile
+    int max_tiles = 0;
+    bool any_full = false;
+    for (const RegionDev& d : R) {
+        max_tiles = std::max(max_tiles, (d.P + 64 * TPIX - 1) / (64 * TPIX));
+        any_full = any_full || d.P >= 64 * TPIX;
+    }
+    if (mode != VAMP_GAUSS3 && any_full) {
+        if (c->f32) HIP_TRY(c->uf_d.ensure(N));
+        else HIP_TRY(c->u_d.ensure(N));
+        HIP_TRY(c->geo_d.ensure(N / (64 * TPIX) + 1));
+        VAMP_FOR_F32(c->f32, hipLaunchKernelGGL((k_tile_tables<F32>), dim3((unsigned)max_tiles, (unsigned)n_regions), dim3(64 * TPIX), 0,
+                                                c->stream, c->regions_d.get(), c->x_d.get(), c->xf_d.get(), c->u_d.get(),
+                                                c->uf_d.get(), c->geo_d.get()));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));      // (the stream may be exchanged before the first sweep)
+    }
     // the launch classes of both partitions, with their region lists on the device
     for (int which = 0; which < 2; ++which) {
         const vamp::plan::ClassPlan& pl = which ? c->plan_small : c->plan;
