@@ -57,3 +57,19 @@ extern "C" void voigt_H_table32_host(int64_t n, const double* x, const double* y
         out[i] = (double)vamp::taylor_table32_eval(tab, (float)fabs(x[i]));
     }
 }
+// The far-field node evaluation's pair form (ff_frac2 of the sweep: two M-level fractions on one reciprocal) and the
+// one-level form beyond X_FAR, as sqrt(pi) H like every evaluator of the header.  M in {2, 3, 4, 6}.
+extern "C" void voigt_jfrac_x2_host(int M, int64_t n, const double* x0, const double* x1, const double* y, double* h0, double* h1) {
+    for (int64_t i = 0; i < n; ++i) {
+        const double r20 = fma(x0[i], x0[i], y[i] * y[i]), r21 = fma(x1[i], x1[i], y[i] * y[i]);
+        switch (M) {
+            case 2: vamp::voigt_jfrac_x2<2>(x0[i], x1[i], y[i], r20, r21, h0[i], h1[i]); break;
+            case 3: vamp::voigt_jfrac_x2<3>(x0[i], x1[i], y[i], r20, r21, h0[i], h1[i]); break;
+            case 4: vamp::voigt_jfrac_x2<4>(x0[i], x1[i], y[i], r20, r21, h0[i], h1[i]); break;
+            default: vamp::voigt_jfrac_x2<6>(x0[i], x1[i], y[i], r20, r21, h0[i], h1[i]); break;
+        }
+    }
+}
+extern "C" void voigt_far_host(int64_t n, const double* x, const double* y, double* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = vamp::voigt_far(x[i], y[i], fma(x[i], x[i], y[i] * y[i]));
+}

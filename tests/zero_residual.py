@@ -96,10 +96,14 @@ def tile_max(v):
 
 
 def make_case(name, x, truth, K, mode=vo.MODE_VOIGT4, dtype="f64", nbz=None, sample_sd=False, splits=(), pad=0.0,
-              data_shift=None):
+              data_shift=None, probe_tile=None):
     """One zero-residual region.  ``pad``: the centre bounds widened by this much beyond the grid (lines centred off the
     grid); ``nbz``: [l_fixed, line, x_origin, x_scale].  ``data_shift``: added to f* after the allowance is built (the
-    negative controls)."""
+    negative controls).  ``probe_tile`` (the probe cases of tests/ff_visibility.py only): the check is localised to that
+    tile -- HUGE_NOISE at every other pixel -- and the allowance inside it is the one derived above with its two global
+    terms made local, never larger than the default one: eps_ctr counts only the lines whose Taylor table covers the
+    pixel (|z|^2 < 64, as the comment above ALLOWANCE says), and the fp32 factor is sqrt(TILE), the pixels the check
+    sums over, instead of sqrt(P)."""
     x = np.ascontiguousarray(x, dtype=np.float64)
     P = x.size
     lo, hi = float(x.min()), float(x.max())
@@ -115,7 +119,14 @@ def make_case(name, x, truth, K, mode=vo.MODE_VOIGT4, dtype="f64", nbz=None, sam
     assert np.all(np.isfinite(f)) and np.isfinite(vo.log_prior(r0, np.append(truth, 0.5) if sample_sd else truth)), name
     eps_abs, eps_rel, eps_ctr = ALLOWANCE[dtype]
     peaks = line_peaks(r0, truth)
-    sigma = eps_abs + f * (eps_rel * tile_max(tau) + eps_ctr * peaks.sum())
+    ctr = peaks.sum()
+    if probe_tile is not None:
+        assert mode == vo.MODE_VOIGT4 and not sample_sd, name
+        t4 = truth.reshape(K, 4)
+        s_k, y_k = 2.0 * vo.SQRT_LN2 / t4[:, 3], t4[:, 2] * vo.SQRT_LN2 / t4[:, 3]
+        covers = np.abs(x[None, :] - t4[:, 1, None]) * s_k[:, None] < np.sqrt(np.maximum(64.0 - y_k ** 2, 0.0))[:, None]
+        ctr = (peaks[:, None] * covers).sum(0)
+    sigma = eps_abs + f * (eps_rel * tile_max(tau) + eps_ctr * ctr)
     if dtype == "f32":
         comps = vo.native_components(r0, truth)
         px = np.median(np.abs(np.diff(x))) if P > 1 else 1.0
@@ -126,7 +137,11 @@ def make_case(name, x, truth, K, mode=vo.MODE_VOIGT4, dtype="f64", nbz=None, sam
         for s in (1.0, -1.0):
             rs = dataclasses.replace(r0, x=x + s * h)
             slope = np.maximum(slope, np.abs(vo.component_taus(rs, truth) - taus).sum(0))
-        sigma = (sigma + f * slope) * math.sqrt(P)
+        sigma = (sigma + f * slope) * math.sqrt(P if probe_tile is None else min(P, TILE))
+    if probe_tile is not None:
+        inside = np.arange(P) // TILE == probe_tile
+        assert inside.any(), (name, probe_tile)
+        sigma = np.where(inside, sigma, HUGE_NOISE)
     flux = f if data_shift is None else f + data_shift(sigma)
     region = dataclasses.replace(r0, flux=flux, noise=sigma)
     return Case(name, region, truth, tau, sigma, dtype, None if nbz is None else np.asarray(nbz, dtype=np.float64),

@@ -817,11 +817,16 @@ __device__ __forceinline__ void ff_frac2(const double (&X)[2], const double (&y)
 // same bits from about six vector instructions fewer per call.
 template <bool GUARD = true>
 __device__ __forceinline__ void ff_eval2(const double (&Xin)[2], const double (&y)[2], double (&H)[2], const double* ec) {
-    double X[2], r2[2];
+    // The clamp bounds the fractions' argument in BOTH coordinates: the two slots share one reciprocal of d0 d1 (ff_frac2),
+    // so a denominator that overflows -- X or y beyond ~1e38; y = L sqrt(ln 2) / G is unbounded where L is the region's
+    // and G -> 0 (NBZ3) -- would turn its PARTNER's value into NaN, and the partner is not patched.  A walker without the
+    // reach bit has X <= X_FAR and y = (L / 2) s <= 1.2 X_FAR (L <= fwhm_max): nothing to bound in the unguarded copy.
+    double X[2], yc[2], r2[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         X[t] = GUARD ? fmin(Xin[t], vamp::X_FAR) : Xin[t];       // lanes hold different lines: guard the promotion
-        r2[t] = fma(X[t], X[t], y[t] * y[t]);
+        yc[t] = GUARD ? fmin(y[t], vamp::X_FAR) : y[t];
+        r2[t] = fma(X[t], X[t], yc[t] * yc[t]);
     }
     const double lo = fmin(r2[0], r2[1]);
     // the fractions' ranges for NODE values: 4e-13 / 2e-13 / 9e-13 of the value at the lower ends (the m-level fraction is
@@ -829,19 +834,19 @@ __device__ __forceinline__ void ff_eval2(const double (&Xin)[2], const double (&
     // hold 2e-15) -- the series these values feed reproduce a wing to 3e-11 of its value
     constexpr double N_M4 = VAMP_FF_R2_M4, N_M3 = VAMP_FF_R2_M3, N_M2 = VAMP_FF_R2_M2;
     if (__any(lo < N_M3)) {
-        if (__any(lo < N_M4)) ff_frac2<6>(X, y, r2, H);
-        else ff_frac2<4>(X, y, r2, H);
+        if (__any(lo < N_M4)) ff_frac2<6>(X, yc, r2, H);
+        else ff_frac2<4>(X, yc, r2, H);
     } else if (__any(lo < N_M2)) {
-        ff_frac2<3>(X, y, r2, H);
+        ff_frac2<3>(X, yc, r2, H);
     } else {
-        ff_frac2<2>(X, y, r2, H);               // valid (more than accurate) beyond 1e8 too, up to X_FAR
+        ff_frac2<2>(X, yc, r2, H);              // valid (more than accurate) beyond 1e8 too, up to X_FAR
     }
     if constexpr (!GUARD) return;
-    const double hi = fmax(Xin[0], Xin[1]), ymin = fmin(y[0], y[1]);
-    if (__any(hi > vamp::X_FAR)) {
+    const double hi = fmax(fmax(Xin[0], Xin[1]), fmax(y[0], y[1])), ymin = fmin(y[0], y[1]);
+    if (__any(hi > vamp::X_FAR)) {              // either coordinate beyond X_FAR: |z|^2 >= R2_M1, voigt_far's range
 #pragma unroll
         for (int t = 0; t < 2; ++t)
-            if (Xin[t] > vamp::X_FAR) H[t] = vamp::voigt_far(Xin[t], y[t], fma(Xin[t], Xin[t], y[t] * y[t]));
+            if (Xin[t] > vamp::X_FAR || y[t] > vamp::X_FAR) H[t] = vamp::voigt_far(Xin[t], y[t], fma(Xin[t], Xin[t], y[t] * y[t]));
     }
     if (__any(ymin < vamp::Y_TINY)) {           // the fractions miss e^{-x^2}; it matters for y < ~1e-11 near |z| = 8
 #pragma unroll
@@ -3184,6 +3189,23 @@ long long vampdbg_launch_plan(vamp_ctx* c, long long movers_per_region, int entr
         ++n;
     }
     return n;
+}
+
+// Test hook, not part of the header: the context's far-field tables (k_tile_tables) as vamp_set_regions left them.  With N
+// the pixels of all regions: u_out [N] (fp64 contexts) or uf_out [N] (fp32 contexts; the other pointer is not touched),
+// geo_out [2 (N / 256 + 1)] as (mid, +-half) pairs.  Host code only: three copies.  Returns the number of geo slots, 0
+// when the context holds no tables (no full tile, or Gaussian lines), or an error code.
+long long vampdbg_tile_tables(vamp_ctx* c, double* u_out, float* uf_out, double* geo_out) {
+    if (!c || !geo_out || !(c->f32 ? (void*)uf_out : (void*)u_out)) return fail(VAMP_ERR_ARG, "vampdbg_tile_tables: bad argument");
+    if (c->regions_h.empty()) return fail(VAMP_ERR_STATE, "vampdbg_tile_tables: call vamp_set_regions first");
+    if (!c->geo_d) return 0;
+    const long long N = c->regions_h.back().pix_off + c->regions_h.back().P;
+    const long long slots = N / (64 * TPIX) + 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->f32) HIP_TRY(hipMemcpy(uf_out, c->uf_d.get(), N * sizeof(float), hipMemcpyDeviceToHost));
+    else HIP_TRY(hipMemcpy(u_out, c->u_d.get(), N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(geo_out, c->geo_d.get(), slots * sizeof(double2), hipMemcpyDeviceToHost));
+    return slots;
 }
 
 int vamp_version(void) { return VAMP_ABI_VERSION; }
