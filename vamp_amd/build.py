@@ -33,6 +33,14 @@ POST_OUT = os.path.join(HERE, "libvamp_post.so")
 POST_DEPS = [POST_SRC, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "..", "include", "vamp_post.h")]
 POST_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
 
+# libvamp_evid.so (include/vamp_evid.h): the log-evidence from tempered ensembles, a fourth library on the same terms;
+# it shares the evaluator (voigt_math.hpp) and the draws (draws.hpp) with the main library
+EVID_SRC = os.path.join(HERE, "csrc", "evidence.hip")
+EVID_OUT = os.path.join(HERE, "libvamp_evid.so")
+EVID_DEPS = [EVID_SRC, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "csrc", "draws.hpp"),
+             os.path.join(HERE, "..", "include", "vamp_evid.h")]
+EVID_FLAGS = POST_FLAGS
+
 
 def _compile(out, src, deps, flags, force, verbose):
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
@@ -56,10 +64,17 @@ def build_post(force=False, verbose=True, out=None, defines=()):
     return _compile(out or POST_OUT, POST_SRC, POST_DEPS, POST_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
+def build_evid(force=False, verbose=True, out=None, defines=()):
+    """libvamp_evid.so; returns its path.  ``out`` / ``defines``: a variant build beside it (tools/bench_evid.py
+    compares the lane widths)."""
+    return _compile(out or EVID_OUT, EVID_SRC, EVID_DEPS, EVID_FLAGS + ["-D" + d for d in defines], force, verbose)
+
+
 def build(force=False, verbose=True):
-    """The three libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
+    """The four libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
     build_diag(force=force, verbose=verbose)
     build_post(force=force, verbose=verbose)
+    build_evid(force=force, verbose=verbose)
     return _compile(OUT, SRC, DEPS, FLAGS, force, verbose)
 
 

@@ -573,6 +573,12 @@ class VPfit():
         self._region, self._shared_ctx = 0, False
         ctx.set_regions(self._x, self._flux, np.ones_like(self._flux), self._n, mode=self._mode, sample_sd=True)
 
+    def log_evidence(self, **kw):
+        """ln Z of this fit's model (vamp_amd.evidence: a ladder of tempered ensembles on the GPU, started from the last
+        ensemble when there is one); keywords as ``evidence.log_evidence``.  The record is kept as ``self.evidence``."""
+        from . import evidence
+        return evidence.fits_evidence([self], device=self.device, **kw)[0]
+
     def chain_covariance(self, n, voigt=False):
         """Per-component 3x3 covariance of (amplitude, sigma, centroid) samples (vpfits.py:432-456)."""
         cov = np.zeros((n, 3, 3))

@@ -54,10 +54,15 @@ class VPregion():
                      voigt=self.voigt, iterations=iterations, thin=thin, burn=burn)
         return fit
 
-    def region_fit(self, verbose=True, iterations=3000, thin=15, burn=300):
+    def region_fit(self, verbose=True, iterations=3000, thin=15, burn=300, criterion='bic', evidence_kw=None):
         """BIC ladder of vpregion.py:42-91: fit n, then n+1, n+2, ... while the mean BIC of the
         three repeats keeps falling; stop early once the mean reduced chi^2 is under ``chi_limit``.
-        The first rung is judged by the LAST of its three BICs, as in the reference (:63)."""
+        The first rung is judged by the LAST of its three BICs, as in the reference (:63).
+        ``criterion='evidence'``: the number of lines is chosen by ln Z instead (``_region_fit_evidence``)."""
+        if criterion == 'evidence':
+            return self._region_fit_evidence(verbose, iterations, thin, burn, evidence_kw or {})
+        if criterion != 'bic':
+            raise ValueError("criterion must be 'bic' or 'evidence'")
         say = print if verbose else (lambda *a, **k: None)
         self._attempt += 1
         say("Setting initial number of lines to: {}".format(self.n))
@@ -85,6 +90,36 @@ class VPregion():
                 say("Reduced chi squared below {}: final n={}.".format(self.chi_limit, self.n))
                 break
         self.fit = kept
+
+    def _evidence_n(self, n, kw):
+        """ln Z of the n-line model of this region: the model ``_fit_n`` fits (free sd, the fit's units)"""
+        from . import evidence
+        freq = np.asarray(self.frequency_array, dtype=np.float64)
+        x = (freq - 0.5 * (freq[0] + freq[-1])) / ((freq[-1] - freq[0]) / (freq.size - 1))
+        kw = dict(kw)
+        kw.setdefault("seed", (evidence.DEFAULT_SEED if self._seed is None else self._seed) + 1000003 * (self._attempt - 1))
+        return evidence.log_evidence({"x": x, "flux": self.flux_array, "noise": None, "sample_sd": True, "n_comp": n,
+                                      "mode": 1 if self.voigt else 0, "region_id": n}, device=self.device or 0, **kw)
+
+    def _region_fit_evidence(self, verbose, iterations, thin, burn, kw):
+        """The ladder of vamp_2.0/vamp_src/phase/phase.py:108-139 made noise-aware: add a component while ln Z rises by
+        more than the two rungs' combined standard error.  The records are kept as ``self.evidences[n]``; the kept fit
+        is produced by ``find_bic`` as on the BIC path, and carries its record as ``fit.evidence``."""
+        from . import evidence
+        say = print if verbose else (lambda *a, **k: None)
+        self._attempt += 1
+        self.evidences = {self.n: self._evidence_n(self.n, kw)}
+        while self.n < evidence.MAX_COMPONENTS:
+            kept, trial = self.evidences[self.n], self._evidence_n(self.n + 1, kw)
+            self.evidences[self.n + 1] = trial
+            rise, se = trial.lnZ - kept.lnZ, float(np.hypot(kept.lnZ_se, trial.lnZ_se))
+            if not rise > se:
+                say("ln Z rose by {:.2f} (combined standard error {:.2f}): keeping n={}.".format(rise, se, self.n))
+                break
+            self.n += 1
+            say("ln Z rose by {:.2f} (combined standard error {:.2f}): n={}.".format(rise, se, self.n))
+        self.fit = self._fit_n(self.n, iterations, thin, burn)
+        self.fit.evidence = self.evidences[self.n]
 
     @staticmethod
     def _release(fit):

@@ -455,6 +455,31 @@ class VPspectrum():
             h5min.write(path, {k: np.array(v) for k, v in post.items()})
         return path
 
+    def evidences(self, **kw):
+        """After ``fit_spectrum``: ln Z of every kept fit's model from ONE GPU call (vamp_amd.evidence; keywords as
+        ``evidence.log_evidence``).  A dict in region order: ``lnZ`` / ``lnZ_se`` / ``lnZ_ti`` / ``n_comp`` [n_regions],
+        ``betas`` [T], ``mean_lnL`` / ``var_lnL`` / ``move_accept`` [n_regions, T], ``swap_accept`` [n_regions, T - 1].  A fit of more
+        lines than the library takes (8) is left out of the call and has NaN rows."""
+        from . import evidence
+        fits = [r.fit for r in self.regions]
+        ok = [f._n <= evidence.MAX_COMPONENTS for f in fits]
+        got = iter(evidence.fits_evidence([f for f, o in zip(fits, ok) if o], device=getattr(self, "device", 0), **kw))
+        recs = [next(got) if o else None for o in ok]
+        T = next((len(r.betas) for r in recs if r is not None), 0)
+        nan = lambda w: np.full(w, np.nan)
+        col = lambda k, w: np.array([nan(w) if r is None else np.atleast_1d(getattr(r, k)) for r in recs], dtype=np.float64).reshape(len(recs), w)
+        return {"lnZ": col("lnZ", 1)[:, 0], "lnZ_se": col("lnZ_se", 1)[:, 0], "lnZ_ti": col("lnZ_ti", 1)[:, 0],
+                "n_comp": np.array([f._n for f in fits], dtype=np.int32),
+                "betas": next((np.array(r.betas) for r in recs if r is not None), np.zeros(0)), "mean_lnL": col("mean_lnL", T),
+                "var_lnL": col("var_lnL", T), "move_accept": col("move_accept", T), "swap_accept": col("swap_accept", max(0, T - 1))}
+
+    def write_evidence(self, ev):
+        """``evidences()``' dict as ``<prefix>evidence.h5`` through vamp_amd/h5min.py; returns the path"""
+        from . import h5min
+        path = self.output_filename + 'evidence.h5'
+        h5min.write(path, {k: np.array(v) for k, v in ev.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
