@@ -19,7 +19,10 @@
  * ln pi(theta): A ~ A exp(-A), c ~ U(c_lo, c_hi), widths ~ U(0, max), sd ~ U(0, 1): the prior the sampler of libvamp_hip.so
  * samples.  ln L(theta): -1/2 chi^2 - 1/2 sum log(2 pi noise_i^2) for known noise (the normalisation is always
  * included), n_pix/2 log(1 / (2 pi sd^2)) - sum (f - m)^2 / (2 sd^2) for the free sd.  Outside the prior ln L is not evaluated
- * and the point is rejected; a ln L that is not finite rejects the point too.  ln Z = log of the integral of pi L.
+ * and the point is rejected; a ln L that is not finite rejects the point too.  A width of exactly 0 (sigma = 0, G_fwhm = 0)
+ * lies on the edge of the prior's closed range and has no ln L: it is reported like a point outside the prior (ln pi = -inf,
+ * ln L = NaN, not evaluated), wherever its centre lies; sd = 0 keeps its ln pi and has ln L = -inf.  L_fwhm = 0 is an ordinary
+ * point: a line of no depth.  ln Z = log of the integral of pi L.
  *
  * Sampler: T = n_temps rungs per region, inverse temperatures betas[0] = 0 < ... < betas[T - 1] = 1 (NULL: the ladder of
  * vamp_evid_default_betas), W = walkers each.  Rung j samples pi L^beta_j with the red/blue stretch move of libvamp_hip.so

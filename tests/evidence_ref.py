@@ -14,7 +14,9 @@ _M = vo.MASK32
 
 
 def default_betas(T):
-    b = (np.arange(T) / (T - 1.0)) ** (1.0 / 0.3)
+    """the ladder of vamp_evid_default_betas through the C library's pow, as the library takes it: numpy's array power is
+    an ulp off it in places (first at T = 33), and a ladder an ulp off is another trajectory"""
+    b = np.array([math.pow(j / (T - 1.0), 1.0 / 0.3) for j in range(T)])
     b[0], b[-1] = 0.0, 1.0
     return b
 
@@ -33,12 +35,16 @@ def make_region(x, flux, noise, n_comp, mode, sample_sd=False, bounds=None):
 
 def lnlike_lnprior(region, theta):
     """(ln L, ln pi) of one parameter vector: outside the prior (-inf) ln L is NaN, not evaluated; a ln L that is not
-    finite is -inf"""
+    finite is -inf.  A width of exactly 0 lies inside the oracle's prior ([0, max]) and its ln L does not exist (G_fwhm = 0
+    divides by zero in Python floats, sigma = 0 on a pixel gives 0 / 0): -inf as well"""
     theta = np.asarray(theta, dtype=np.float64)
     lp = vo.log_prior(region, theta)
     if not lp > -np.inf:
         return np.nan, -np.inf
-    ll = vo.log_like(region, theta)
+    try:
+        ll = vo.log_like(region, theta)
+    except ZeroDivisionError:
+        ll = np.nan
     return (ll if np.isfinite(ll) else -np.inf), lp
 
 
@@ -124,16 +130,23 @@ def stepping_stone(trace, betas):
     return sum(log_mean_exp((betas[j + 1] - betas[j]) * trace[:, j]) for j in range(len(betas) - 1))
 
 
-def reduce(trace, betas):
-    """the reductions of k_evid_reduce from the kept ln L [n_keep, T, W]"""
+def block_borders(n):
+    """the borders of the 8 time blocks of n kept steps: block b is the kept steps borders[b] .. borders[b + 1] - 1"""
+    return [b * n // N_BLOCKS for b in range(N_BLOCKS + 1)]
+
+
+def reduce(trace, betas, borders=None):
+    """the reductions of k_evid_reduce from the kept ln L [n_keep, T, W]; ``zb``: the block estimates behind ``lnZ_se``
+    (None with fewer than 8 kept steps).  ``borders``: other block borders than the library's (the controls of the tests)"""
     n = trace.shape[0]
     mean, var = trace.mean(axis=(0, 2)), trace.var(axis=(0, 2))
-    se = np.nan
+    se, zb = np.nan, None
     if n >= N_BLOCKS:
-        zb = [stepping_stone(trace[b * n // N_BLOCKS:(b + 1) * n // N_BLOCKS], betas) for b in range(N_BLOCKS)]
-        se = np.std(zb, ddof=1) / math.sqrt(N_BLOCKS)
+        bd = block_borders(n) if borders is None else list(borders)
+        zb = np.array([stepping_stone(trace[bd[b]:bd[b + 1]], betas) for b in range(N_BLOCKS)])
+        se = float(np.std(zb, ddof=1) / math.sqrt(N_BLOCKS))
     ti = float(np.sum(np.diff(betas) * 0.5 * (mean[:-1] + mean[1:])))
-    return {"lnZ": stepping_stone(trace, betas), "lnZ_se": se, "lnZ_ti": ti, "mean_lnL": mean, "var_lnL": var}
+    return {"lnZ": stepping_stone(trace, betas), "lnZ_se": se, "lnZ_ti": ti, "mean_lnL": mean, "var_lnL": var, "zb": zb}
 
 
 def run(regions, region_ids, betas, W, n_steps, burn, swap_every, seed, a=2.0, starts=None):

@@ -18,36 +18,10 @@ import pytest
 
 import evidence_ref as ref
 from conftest import GOLDEN, ROOT, load_golden
+from evidence_cases import SEED, as_dict as _as_dict, check_lnlike as _check_lnlike, synthetic as _synthetic
 from oracle import vamp_oracle as vo
 
 pytestmark = pytest.mark.gpu
-
-SEED = 0x5EED0123456789
-
-
-def _as_dict(R, region_id=0, bounds=True):
-    d = {"x": R.x, "flux": R.flux, "noise": None if R.sample_sd else R.noise, "n_comp": R.n_comp, "mode": R.mode, "sample_sd": R.sample_sd,
-         "region_id": region_id}
-    if bounds:
-        d["bounds"] = (R.c_lo, R.c_hi, R.sigma_max, R.fwhm_max)
-    return d
-
-
-def _check_lnlike(R, theta, bounds, tag):
-    from vamp_amd import evidence
-    got_ll, got_lp = evidence.lnlike(_as_dict(R, bounds=bounds), theta)
-    want_ll, want_lp = ref.lnlike_batch(R, theta)
-    inside = want_lp > -np.inf
-    assert np.array_equal(got_lp > -np.inf, inside), tag
-    assert np.all(got_lp[~inside] == -np.inf) and np.all(np.isnan(got_ll[~inside])), tag
-    err = np.abs(got_lp[inside] - want_lp[inside]) / np.maximum(1.0, np.abs(want_lp[inside]))
-    assert err.size == 0 or err.max() <= 1e-9, (tag, "lnprior", err.max())
-    fin = np.isfinite(want_ll) & inside
-    assert np.array_equal(np.isfinite(got_ll) & inside, fin), tag
-    assert np.all(got_ll[inside & ~fin] == -np.inf), tag
-    err = np.abs(got_ll[fin] - want_ll[fin]) / np.maximum(1.0, np.abs(want_ll[fin]))
-    assert err.size == 0 or err.max() <= 1e-9, (tag, "lnlike", err.max())
-    return int(fin.sum())
 
 
 def test_lnlike_matches_oracle_on_the_golden_cases():
@@ -63,27 +37,6 @@ def test_lnlike_matches_oracle_on_the_golden_cases():
         assert _check_lnlike(R, g[name + "_theta"], False, name) > 0, name           # bounds derived by the library
         seen.add((mode, sd))
     assert seen == {(0, False), (0, True), (1, False), (1, True)}
-
-
-def _synthetic(P, K, mode, sd, descending=False, seed=0):
-    """a region of P pixels with K lines and 40 parameter vectors: prior draws, some pushed outside the prior"""
-    rng = np.random.default_rng(100 * P + 10 * K + mode + seed)
-    x = np.arange(float(P)) - 0.37 * P
-    lo, hi = (x[0], x[-1]) if P > 1 else (-3.0, 3.0)
-    lines = [(rng.uniform(0.3, 2.0), rng.uniform(lo, hi), rng.uniform(0.5, 3.0)) for _ in range(K)]
-    flux = np.exp(-sum(vo.gauss_function(x, *ln) for ln in lines)) + 0.05 * rng.standard_normal(P)
-    if descending:
-        x, flux = x[::-1].copy(), flux[::-1].copy()
-    smax = (hi - lo) / 2.0
-    R = ref.make_region(x, flux, np.full(P, 0.05), K, mode, sd, bounds=(lo, hi, smax, smax * 2 * np.sqrt(2 * np.log(2.0))))
-    theta = np.concatenate([ref.prior_draws(R, 7 + j, 10, SEED) for j in range(4)])
-    theta[3, 0] = -0.1                      # A < 0
-    theta[5, 1] = hi + 1.0                  # c outside
-    theta[8, R.q - 1] = 1.01 * (R.sigma_max if mode == 0 else R.fwhm_max)
-    if sd:
-        theta[11, -1] = 1.5
-    theta[13, 2] *= 1e-3                    # a very narrow line
-    return R, theta
 
 
 @pytest.mark.parametrize("P", [1, 15, 16, 17, 63, 64, 65, 300])
