@@ -48,6 +48,7 @@
 #include "host_plan.hpp"
 #include "map_search.hpp"
 #include "voigt_math.hpp"
+#include "ff_predicates.hpp"
 
 #ifndef VAMP_EARLY_LOADS
 #define VAMP_EARLY_LOADS 1
@@ -869,10 +870,12 @@ __device__ __forceinline__ unsigned ff_tile_field(unsigned long long batchmask, 
     const unsigned h = (lane & 32) ? (unsigned)(batchmask >> 32) : (unsigned)batchmask;
     return (h >> (lane & 16)) & 0xffffu;
 }
-template <bool WIDE, bool F32, class LDS>
+//     ZONE (fp64 loop with the lines' Taylor tables): a third mask, bit set = the whole tile lies inside the line's table
+//     zone (vamp::ff_tile_in_zone); the near-line loop consults it for its near lines and skips tile_voigt's votes.
+template <bool WIDE, bool F32, bool ZONE = false, class LDS>
 __device__ __forceinline__ void ff_classify_batch(const LDS& L, TileScratch& Sx, const double2* __restrict__ geo, int K, int lane_, int base,
                                                   int base1, int stride, unsigned wide_all,
-                                                  unsigned long long& farmasks, unsigned long long& widemasks) {
+                                                  unsigned long long& farmasks, unsigned long long& widemasks, unsigned long long& zonemasks) {
     // everything a lane derives from its index is derived here, once per batch, from an opaque copy: hoisted out of
     // the tile loop these values would sit in registers the loop does not have (and come back from scratch)
     int lane = lane_;
@@ -904,6 +907,8 @@ __device__ __forceinline__ void ff_classify_batch(const LDS& L, TileScratch& Sx,
         widemasks = __ballot(my_wide);
         if (my_wide) Sx.widelist[j][__builtin_popcount(ff_tile_field(widemasks, lane) & below)] = (unsigned char)k;
     }
+    zonemasks = 0ull;
+    if constexpr (ZONE) zonemasks = __ballot(vamp::ff_tile_in_zone(my_c, me.s, me.y, mid, half));
     __builtin_amdgcn_wave_barrier();      // (the lists are in LDS; their readers follow in the tiles' iterations)
 }
 // node sums (lanes 0..15 hold them) -> the four local power series of the tile: lane l = 14 q + j < 56 owns
@@ -1047,10 +1052,10 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
     // the lines are classified against FF_BATCH tiles at a time, at the top of every FF_BATCH-th tile (ahead of the
     // previous batch's last tiles the pass would hold its loads in registers the loop does not have)
     for (int batch = base0; batch < base1; batch += FF_BATCH * stride) {
-    unsigned long long farmasks, widemasks;
-    ff_classify_batch<WIDE, false>(L, Sx, geo, K, lane, batch, base1, stride, (unsigned)wide_all, farmasks, widemasks);
+    unsigned long long farmasks, widemasks, zonemasks;
+    ff_classify_batch<WIDE, false, TAB>(L, Sx, geo, K, lane, batch, base1, stride, (unsigned)wide_all, farmasks, widemasks, zonemasks);
 #pragma unroll 1
-    for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX) {
+    for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX, zonemasks >>= KMAX) {
         const int base = batch + j * stride;
         if (base >= base1) break;
         double xi[T], tau[T];
@@ -1094,7 +1099,15 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             double X[T], H[T];
 #pragma unroll
             for (int t = 0; t < T; ++t) X[t] = fabs(xi[t] - ln.c) * ln.s;
-            tile_voigt<T, TAB>(ln, dtab_row<PK>(L, k), X, H, TAB ? tab + k * vamp::TAB_LINE : nullptr, dct + FF_EXP);
+            // the classification has established that every pixel of the tile lies in the line's table zone: the
+            // straight-line path tile_voigt would find for itself (same function, same arguments, same bits: inside
+            // |z| < 8 no cap binds), without the sixteen instructions and four votes it takes to find it
+            if (TAB && (((unsigned)zonemasks >> k) & 1u)) {
+#pragma unroll
+                for (int t = 0; t < T; ++t) H[t] = table_eval(tab + k * vamp::TAB_LINE, X[t]);
+            } else {
+                tile_voigt<T, TAB>(ln, dtab_row<PK>(L, k), X, H, TAB ? tab + k * vamp::TAB_LINE : nullptr, dct + FF_EXP);
+            }
 #pragma unroll
             for (int t = 0; t < T; ++t) tau[t] = fma(ln.amp, H[t], tau[t]);
         }
@@ -1361,7 +1374,8 @@ __device__ __forceinline__ void sweep_range_f32_ff(const RegionDev& R, const typ
     // (fp32: the node values are W4 regions I / II, valid from |x| + y = 5.5 -- no |z| >= 8 condition as for the fp64
     //  fractions: a line is far once the tile is outside its Gaussian core, |z|^2 >= VAMP_MID_Z2)
     unsigned long long farmasks, widemasks;
-    ff_classify_batch<false, true>(L, Sx, geo, K, lane, batch, base1, stride, 0u, farmasks, widemasks);
+    unsigned long long zonemasks;      // (fp64 loop only: constant zero here)
+    ff_classify_batch<false, true>(L, Sx, geo, K, lane, batch, base1, stride, 0u, farmasks, widemasks, zonemasks);
 #pragma unroll 1
     for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX) {
         const int base = batch + j * stride;
