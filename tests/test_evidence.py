@@ -121,6 +121,7 @@ def test_build_makes_four_libraries():
     for name in ("libvamp_hip.so", "libvamp_diag.so", "libvamp_post.so", "libvamp_evid.so"):
         assert os.path.exists(os.path.join(ROOT, "vamp_amd", name)), name
     assert set(vb.EVID_DEPS) == {vb.EVID_SRC, os.path.join(vb.HERE, "csrc", "voigt_math.hpp"), os.path.join(vb.HERE, "csrc", "draws.hpp"),
+                                 os.path.join(vb.HERE, "csrc", "side_call.hpp"), os.path.join(vb.HERE, "csrc", "lane_group.hpp"),
                                  os.path.join(vb.HERE, "..", "include", "vamp_evid.h")}
     assert vb.EVID_FLAGS == vb.POST_FLAGS
 
@@ -170,7 +171,8 @@ def test_other_libraries_untouched(evid_lib):
     exported = sorted(set(re.findall(r"\bT (vamp_[a-z0-9_]+)\b", out)))
     assert exported == sorted(set(re.findall(r"\b(vamp_[a-z0-9_]+)\s*\(", _header_src("vamp_hip.h"))))
     src = open(os.path.join(ROOT, "vamp_amd", "csrc", "evidence.hip")).read()
-    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../include/vamp_evid.h", "draws.hpp", "voigt_math.hpp"}
+    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../include/vamp_evid.h", "draws.hpp", "lane_group.hpp", "side_call.hpp",
+                                                               "voigt_math.hpp"}
 
 
 def test_arguments_are_checked_before_any_device_call(evid_lib):

@@ -10,7 +10,10 @@ the call includes its scratch allocation, the two kernels and the copy of the re
 call on host arrays (adds the staging copy), the numpy restatement's host time (tests/chain_diag_ref.py;
 for the headline measured on a slice of the walkers and scaled by the walker count), the FMAs of the lag sums
 (sum W N (N+1)/2 D) and bytes read (8 sum N W D), and the fractions of the fp64 VALU rate (39.3 T lane-ops/s)
-and of 8 TB/s these imply at the event time.   python tools/bench_diag.py [--reps 5]"""
+and of 8 TB/s these imply at the event time.
+
+--lib PATH times another build of the library (an earlier commit's, to compare the whole call: at the q1422 shape it
+is bound by its host side).   python tools/bench_diag.py [--reps 5]"""
 import argparse
 import json
 import os
@@ -24,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import chain_diag_ref as ref  # noqa: E402
-from vamp_amd import diagnostics  # noqa: E402
+from vamp_amd import _diag_lib, diagnostics  # noqa: E402
 
 VALU_FP64 = 39.3e12
 HBM = 8.0e12
@@ -67,9 +70,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-headline", action="store_true")
+    ap.add_argument("--lib", default=None, help="another build of libvamp_diag.so")
+    ap.add_argument("--label", default="default")
     a = ap.parse_args()
+    if a.lib:
+        _diag_lib.LIB_PATH = os.path.abspath(a.lib)
     dev = torch.device("cuda", 0)
-    out = {"metric": "chain_diagnostics"}
+    out = {"metric": "chain_diagnostics", "label": a.label}
     # q1422-shaped ragged set
     rng = np.random.default_rng(1422)
     Ds = rng.choice([4, 4, 4, 7], size=421)

@@ -1,19 +1,15 @@
 """ctypes binding of libvamp_diag.so (include/vamp_diag.h): the chain diagnostics.
 
-The same rules as ``_lib``: no fallback (a missing library raises, every call needs a GPU), and the
-library is loaded after torch so that it binds the ROCm runtime torch has mapped -- the one
-libvamp_hip.so binds too, so that a device pointer from ``HipContext.run_dev`` means the same thing to
-both libraries ("Two ROCm runtimes in one process").
+Loading, the torch-order warning and the error check are ``_sidelib``'s, and so are their rules.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-import sys
-import warnings
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libvamp_diag.so")
+from . import _sidelib
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvamp_diag.so")
 
 # name -> (restype, argtypes); mirrors include/vamp_diag.h one to one
 SIGNATURES = {
@@ -25,45 +21,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]),
 }
 
-_lib = None
-
-
-def bind(path):
-    lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-def load():
-    """Load libvamp_diag.so and attach the prototypes.  Raises if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} not found: the HIP extension is not built (run `python -c 'import "
-            "__graft_entry__ as g; g.build()'`).  vamp_amd has no CPU fallback.")
-    if "torch" not in sys.modules and not os.environ.get("VAMP_NO_IMPORT_ORDER_WARNING"):
-        import importlib.util
-        try:
-            has_torch = importlib.util.find_spec("torch") is not None
-        except (ImportError, ValueError):
-            has_torch = False
-        if has_torch:
-            warnings.warn("vamp_amd: libvamp_diag.so is being loaded before torch.  If this process imports torch later it "
-                          "will hold two ROCm runtimes: `import torch` first (INTEGRATION.md, \"Two ROCm runtimes in one "
-                          "process\"); VAMP_NO_IMPORT_ORDER_WARNING=1 silences this.", RuntimeWarning, stacklevel=3)
-    _lib = bind(LIB_PATH)
-    return _lib
-
 
 class DiagError(RuntimeError):
     pass
 
 
-def check(rc, lib=None):
-    if rc != 0:
-        raise DiagError("libvamp_diag error: " + (lib or load()).vamp_diag_last_error().decode("utf-8", "replace"))
+bind, load, check = _sidelib.loader(__name__, "diag", DiagError)

@@ -19,27 +19,33 @@ DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("ff_matrix.inc", "ff_mat
 # (profiles/r03_b_f32_variants.txt; MI355X_MICROARCH.md lists packed fp32 VALU as an anti-lever).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-shared", "-fPIC"]
 
+# The three side libraries share their flags, the frame of their entry points (side_call.hpp) and -- the posterior and
+# the evidence -- the lane-group evaluator (lane_group.hpp): an edit of a shared header rebuilds what includes it
+SIDE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
+SIDE_CALL = os.path.join(HERE, "csrc", "side_call.hpp")
+LANE_GROUP = os.path.join(HERE, "csrc", "lane_group.hpp")
+
 # libvamp_diag.so (include/vamp_diag.h): the chain diagnostics, a library of its own with its own dependency list,
 # so that an edit of chain_diag.hip rebuilds it in seconds and leaves the main library alone
 DIAG_SRC = os.path.join(HERE, "csrc", "chain_diag.hip")
 DIAG_OUT = os.path.join(HERE, "libvamp_diag.so")
-DIAG_DEPS = [DIAG_SRC, os.path.join(HERE, "..", "include", "vamp_diag.h")]
-DIAG_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
+DIAG_DEPS = [DIAG_SRC, SIDE_CALL, os.path.join(HERE, "..", "include", "vamp_diag.h")]
+DIAG_FLAGS = SIDE_FLAGS
 
 # libvamp_post.so (include/vamp_post.h): the posterior summaries, a third library on the same terms; it shares
 # voigt_math.hpp with the main library, so an edit of the evaluator rebuilds both
 POST_SRC = os.path.join(HERE, "csrc", "posterior.hip")
 POST_OUT = os.path.join(HERE, "libvamp_post.so")
-POST_DEPS = [POST_SRC, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "..", "include", "vamp_post.h")]
-POST_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
+POST_DEPS = [POST_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "..", "include", "vamp_post.h")]
+POST_FLAGS = SIDE_FLAGS
 
 # libvamp_evid.so (include/vamp_evid.h): the log-evidence from tempered ensembles, a fourth library on the same terms;
 # it shares the evaluator (voigt_math.hpp) and the draws (draws.hpp) with the main library
 EVID_SRC = os.path.join(HERE, "csrc", "evidence.hip")
 EVID_OUT = os.path.join(HERE, "libvamp_evid.so")
-EVID_DEPS = [EVID_SRC, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "csrc", "draws.hpp"),
+EVID_DEPS = [EVID_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "csrc", "draws.hpp"),
              os.path.join(HERE, "..", "include", "vamp_evid.h")]
-EVID_FLAGS = POST_FLAGS
+EVID_FLAGS = SIDE_FLAGS
 
 
 def _compile(out, src, deps, flags, force, verbose):

@@ -22,10 +22,13 @@
 #include <vector>
 
 #include "../../include/vamp_diag.h"
+#include "side_call.hpp"
 
 #define VAMP_DIAG_API extern "C" __attribute__((visibility("default")))
 
 namespace {
+
+using namespace vamp::side;
 
 constexpr int kStats = 5;          // per chunk: sequences, mean of their means, M2 of their means, sum of s^2, stuck walkers
 constexpr int kMaxWc = 64;         // walkers per chunk at most
@@ -295,41 +298,6 @@ __global__ __launch_bounds__(256) void k_chain_finish(const Pair* __restrict__ p
     }
 }
 
-thread_local std::string g_err;
-
-int fail(const std::string& msg) {
-    g_err = msg;
-    return -1;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            (void)hipGetLastError();                                                                    \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                             \
-        }                                                                                               \
-    } while (0)
-
-struct DevBuf {                    // released on every exit path
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-struct DeviceRestore {             // the caller's current device, put back on every exit path
-    int dev = -1;
-    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
-};
-
-template <class T>
-int upload(DevBuf& buf, const std::vector<T>& v, hipStream_t st) {
-    if (v.empty()) return 0;
-    HIP_TRY(hipMalloc(&buf.p, v.size() * sizeof(T)));
-    HIP_TRY(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
-    return 0;
-}
-
 int walkers_per_chunk(int N) {
     const int Wc = N <= kSmallN ? kTileSmall / (N + 16) : kTileLarge / (N + 32);
     return Wc < kMaxWc ? Wc : kMaxWc;
@@ -345,13 +313,14 @@ VAMP_DIAG_API int vamp_diag_chains(int device, void* hip_stream, int n_groups, c
                                    const int64_t* ld, const int32_t* n_keep, const int32_t* walkers, const int32_t* ndim,
                                    double c, double* tau, double* n_eff, double* r_hat, int32_t* window, uint8_t* reliable) {
     g_err.clear();
-    if (n_groups <= 0) return fail("vamp_diag_chains: n_groups must be positive");
+    const std::string fn = "vamp_diag_chains: ";
+    if (n_groups <= 0) return fail(fn + "n_groups must be positive");
     if (!base || !ld || !n_keep || !walkers || !ndim || !tau || !n_eff || !r_hat || !window || !reliable)
-        return fail("vamp_diag_chains: NULL argument");
-    if (!(c > 0.0) || !std::isfinite(c)) return fail("vamp_diag_chains: c must be a positive finite number");
+        return fail(fn + "NULL argument");
+    if (!(c > 0.0) || !std::isfinite(c)) return fail(fn + "c must be a positive finite number");
     long long n_out = 0;
     for (int g = 0; g < n_groups; ++g) {
-        const std::string at = "vamp_diag_chains: group " + std::to_string(g) + ": ";
+        const std::string at = fn + "group " + std::to_string(g) + ": ";
         if (!base[g]) return fail(at + "NULL base pointer");
         if (n_keep[g] <= 0 || walkers[g] <= 0 || ndim[g] <= 0) return fail(at + "n_keep, walkers and ndim must be positive");
         if (n_keep[g] > VAMP_DIAG_MAX_SAMPLES)
@@ -360,7 +329,7 @@ VAMP_DIAG_API int vamp_diag_chains(int device, void* hip_stream, int n_groups, c
         if (ld[g] < (int64_t)walkers[g] * ndim[g]) return fail(at + "ld < walkers * ndim");
         n_out += ndim[g];
     }
-    if (n_out > (1LL << 30)) return fail("vamp_diag_chains: too many outputs");
+    if (n_out > (1LL << 30)) return fail(fn + "too many outputs");
 
     // host-side answers first: N < 4 is NaN everywhere
     for (int g = 0, o = 0; g < n_groups; ++g)
@@ -371,36 +340,17 @@ VAMP_DIAG_API int vamp_diag_chains(int device, void* hip_stream, int n_groups, c
         }
 
     DeviceRestore restore;
-    int ndev = 0, prev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("vamp_diag_chains: no HIP device " + std::to_string(device));
-    HIP_TRY(hipGetDevice(&prev));
-    restore.dev = prev;
-    HIP_TRY(hipSetDevice(device));
+    if (set_device(fn, device, restore)) return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
 
-    // device view of every group: staged (host input) or as given
-    std::vector<const double*> dbase(n_groups, nullptr);
+    // device view of every group: staged (host input; N < 4 groups are answered above and not staged) or as given
+    std::vector<const double*> dbase(base, base + n_groups);
     DevBuf staging;
     if (!is_device) {
-        std::vector<long long> off(n_groups, 0);
-        long long total = 0;
-        for (int g = 0; g < n_groups; ++g) {
-            if (n_keep[g] < 4) continue;
-            off[g] = total;
-            total += (long long)(n_keep[g] - 1) * ld[g] + (long long)walkers[g] * ndim[g];
-        }
-        if (total > 0) {
-            HIP_TRY(hipMalloc(&staging.p, total * sizeof(double)));
-            for (int g = 0; g < n_groups; ++g) {
-                if (n_keep[g] < 4) continue;
-                const long long len = (long long)(n_keep[g] - 1) * ld[g] + (long long)walkers[g] * ndim[g];
-                HIP_TRY(hipMemcpyAsync(staging.as<double>() + off[g], base[g], len * sizeof(double), hipMemcpyHostToDevice, st));
-                dbase[g] = staging.as<double>() + off[g];
-            }
-        }
-    } else {
-        for (int g = 0; g < n_groups; ++g) dbase[g] = base[g];
+        std::vector<long long> len(n_groups, 0);
+        for (int g = 0; g < n_groups; ++g)
+            if (n_keep[g] >= 4) len[g] = chain_span(n_keep[g], ld[g], walkers[g], ndim[g]);
+        if (stage_chains(len, base, st, staging, dbase)) return -1;
     }
 
     // (group, parameter) pairs and their (pair, chunk) tasks, by path
@@ -430,7 +380,7 @@ VAMP_DIAG_API int vamp_diag_chains(int device, void* hip_stream, int n_groups, c
         }
     }
     if (pairs.empty()) return 0;
-    if (tasks_small.size() > 0x7fffffff || tasks_large.size() > 0x7fffffff) return fail("vamp_diag_chains: too many chunks");
+    if (tasks_small.size() > 0x7fffffff || tasks_large.size() > 0x7fffffff) return fail(fn + "too many chunks");
 
     DevBuf d_pairs, d_small, d_large, d_rho, d_stat, d_out, d_win, d_rel;
     const int np = (int)pairs.size();

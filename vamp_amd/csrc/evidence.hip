@@ -7,7 +7,7 @@
 //   k_evid_steps   one workgroup per (region, rung), the rung's walkers, ln L and ln pi in LDS, swap_every full
 //                  stretch steps per launch.  A wavefront -- or, for short regions of few lines, a 16-lane group -- owns
 //                  one mover at a time: the draws of draws.hpp, the proposal, its line records and near-axis tables
-//                  staged as k_post_eval stages them, the pixels walked a round of lanes at a time, chi^2 reduced
+//                  staged by lane_group.hpp, the pixels walked a round of lanes at a time, chi^2 reduced
 //                  by a butterfly of fixed order.  The lane width depends on (n_pix, K) only.
 //   k_evid_swap    one thread per (region, pair, walker), after every launch of k_evid_steps but the last
 //   k_evid_reduce  one workgroup per region: per-rung moments, the stepping-stone estimate with its block standard
@@ -17,12 +17,13 @@
 
 #include <cmath>
 #include <cstdint>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/vamp_evid.h"
 #include "draws.hpp"
+#include "lane_group.hpp"
+#include "side_call.hpp"
 #include "voigt_math.hpp"
 
 #define VAMP_EVID_API extern "C" __attribute__((visibility("default")))
@@ -34,10 +35,12 @@
 
 namespace {
 
+using namespace vamp::side;
+using vamp::lds_fence;
+
 constexpr int kBlock = 256;                // four wavefronts
 constexpr int kWaves = kBlock / 64;
 constexpr int kRec = 7;                    // doubles of a line record: centre, scale, damping, amplitude, pole, h y, ln prior
-constexpr int kNarrowLanes = 16, kNarrowMaxPix = 32, kNarrowMaxK = 4;
 constexpr int kHead = 2;                   // doubles in front of the state of k_evid_steps
 constexpr int kEvalRows = 64;              // rows of parameters per workgroup of k_evid_eval
 constexpr int kMaxD = 4 * VAMP_EVID_MAX_COMPONENTS + 1;
@@ -53,7 +56,7 @@ struct Reg {                       // one region
     double c_lo, c_hi, w_max, lp_c, lp_w, norm_const;
     long long theta_off;           // of the region's [T][W][D] state (k_evid_eval: of its rows)
     long long out_off;             // of the region's [T][W] ln L / ln pi
-    int P, K, q, D, sd, lanes;     // lanes that own a mover: 64 or kNarrowLanes
+    int P, K, q, D, sd, lanes;     // lanes that own a mover (vamp::group_lanes)
     unsigned rid;                  // region_id
 };
 
@@ -68,12 +71,6 @@ __host__ __device__ inline unsigned region_rng_id(const Sampler& S, int) { retur
 
 // LDS of one mover: the proposal, the line records, the near-axis tables
 __host__ __device__ constexpr int slot_doubles(int D, int K, bool voigt) { return D + K * kRec + (voigt ? K * vamp::DTAB_N : 0); }
-
-__device__ __forceinline__ void lds_fence() {      // LDS traffic between the lanes of one wavefront
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ double xexp_logp(double v) {        // log(v exp(-v)), literally; -inf below 0
     if (!(v >= 0.0) || !isfinite(v)) return -INFINITY;
@@ -121,26 +118,14 @@ __device__ __forceinline__ void eval_point(const Reg& R, const double* q, double
         if (R.sd) lp += uniform_logp(q[R.D - 1], 0.0, 1.0, 0.0);
     }
     const bool good = valid && lp > -INFINITY;     // (false for NaN)
-    if (good && voigt)
-        for (int e = gl; e < K * vamp::DTAB_N; e += lanes) {
-            const int k = e / vamp::DTAB_N, n = e - k * vamp::DTAB_N;
-            dtab[e] = vamp::core_dtab_entry(n, rec[k * kRec + 2]);
-        }
+    if (good && voigt) vamp::fill_dtab<kRec>(dtab, rec, K, gl, lanes);
     lds_fence();
     double chi = 0.0;
     if (good)
         for (int p = gl; p < R.P; p += lanes) {
             const double xi = R.x[p];
             double tau = 0.0;
-            for (int k = 0; k < K; ++k) {
-                const double* r = rec + k * kRec;
-                if (voigt) {
-                    tau += r[3] * vamp::voigt_Hs(fabs(xi - r[0]) * r[1], r[2], dtab + k * vamp::DTAB_N, r[4], r[5]);
-                } else {
-                    const double u = (xi - r[0]) * r[1];
-                    tau += r[3] * exp(-0.5 * (u * u));
-                }
-            }
+            for (int k = 0; k < K; ++k) tau += vamp::line_tau(voigt, xi, rec + k * kRec, dtab + k * vamp::DTAB_N);
             const double d = (R.f[p] - exp(-tau)) * R.wt[p];
             chi = fma(d, d, chi);
         }
@@ -206,8 +191,9 @@ __global__ __launch_bounds__(kBlock) void k_evid_eval(const Reg* __restrict__ re
     const int g = blockIdx.x / blocks_per_region, jb = blockIdx.x - g * blocks_per_region;
     const Reg R = regs[g];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int lanes = R.lanes, nsub = 64 / lanes;
-    const int sub = lane / lanes, gl = lane - sub * lanes;
+    const int lanes = R.lanes;
+    const vamp::LaneGroup lg = vamp::lane_group(lane, lanes);
+    const int nsub = lg.nsub, sub = lg.sub, gl = lg.gl;
     const bool voigt = R.q == 4;
     double* q = lds + (size_t)(wave * nsub + sub) * slot_doubles(R.D, R.K, voigt);
     double* rec = q + R.D;
@@ -240,8 +226,9 @@ __global__ __launch_bounds__(kBlock) void k_evid_steps(const Reg* __restrict__ r
     const double beta = betas[j];
     const int D = R.D, tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
-    const int lanes = R.lanes, nsub = 64 / lanes;
-    const int sub = lane / lanes, gl = lane - sub * lanes;
+    const int lanes = R.lanes;
+    const vamp::LaneGroup lg = vamp::lane_group(lane, lanes);
+    const int nsub = lg.nsub, sub = lg.sub, gl = lg.gl;
     const bool voigt = R.q == 4;
     double* X = lds + kHead;
     double* ll = X + (size_t)W * D;
@@ -330,41 +317,15 @@ __global__ __launch_bounds__(kBlock) void k_evid_swap(const Reg* __restrict__ re
     atomicAdd(&nswap[g * (T - 1) + j], 1u);
 }
 
-// sum / maximum over the workgroup in a fixed order
-__device__ inline double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-__device__ inline double block_max(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = fmax(red[tid], red[tid + o]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // log mean exp(db * ln L) over rung j's kept steps [t0, t1)
 __device__ inline double log_mean_exp(const double* tr, int T, int W, int j, int t0, int t1, double db, double* red) {
     const int n = (t1 - t0) * W;
     double m = -INFINITY;
     for (int i = threadIdx.x; i < n; i += kBlock) m = fmax(m, db * tr[((long long)(t0 + i / W) * T + j) * W + i % W]);
-    m = block_max(m, red);
+    m = vamp::block_max<kBlock>(m, red);
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += kBlock) s += exp(db * tr[((long long)(t0 + i / W) * T + j) * W + i % W] - m);
-    s = block_sum(s, red);
+    s = vamp::block_sum<kBlock>(s, red);
     return m + log(s / (double)n);
 }
 
@@ -382,10 +343,10 @@ __global__ __launch_bounds__(kBlock) void k_evid_reduce(const double* __restrict
     for (int j = 0; j < T; ++j) {
         double s = 0.0;
         for (int i = tid; i < n; i += kBlock) s += tr[((long long)(i / W) * T + j) * W + i % W];
-        const double mean = block_sum(s, red) / (double)n;
+        const double mean = vamp::block_sum<kBlock>(s, red) / (double)n;
         s = 0.0;
         for (int i = tid; i < n; i += kBlock) { const double d = tr[((long long)(i / W) * T + j) * W + i % W] - mean; s = fma(d, d, s); }
-        const double var = block_sum(s, red) / (double)n;
+        const double var = vamp::block_sum<kBlock>(s, red) / (double)n;
         if (tid == 0) {
             means[j] = mean;
             mean_out[g * T + j] = mean;
@@ -423,69 +384,11 @@ __global__ __launch_bounds__(kBlock) void k_evid_reduce(const double* __restrict
     }
 }
 
-thread_local std::string g_err;
-
-int fail(const std::string& msg) {
-    g_err = msg;
-    return -1;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            (void)hipGetLastError();                                                                    \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                             \
-        }                                                                                               \
-    } while (0)
-
-struct DevBuf {                    // released on every exit path
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-struct DeviceRestore {             // the caller's current device, put back on every exit path
-    int dev = -1;
-    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
-};
-
-template <class T>
-int upload(DevBuf& buf, const std::vector<T>& v, hipStream_t st) {
-    if (v.empty()) return 0;
-    HIP_TRY(hipMalloc(&buf.p, v.size() * sizeof(T)));
-    HIP_TRY(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
-    return 0;
-}
-
-constexpr int kNarrowSlots = kWaves * (64 / kNarrowLanes) * slot_doubles(4 * kNarrowMaxK + 1, kNarrowMaxK, true);
+constexpr int kNarrowSlots = kWaves * (64 / vamp::kNarrowLanes) * slot_doubles(4 * vamp::kNarrowMaxK + 1, vamp::kNarrowMaxK, true);
 constexpr int kWideSlots = kWaves * slot_doubles(kMaxD, VAMP_EVID_MAX_COMPONENTS, true);
 constexpr size_t kStepsMaxLds =
     sizeof(double) * (size_t)(kHead + VAMP_EVID_MAX_WALKERS * (kMaxD + 2) + (kNarrowSlots > kWideSlots ? kNarrowSlots : kWideSlots));
 constexpr size_t kDefaultLds = 64 * 1024;
-constexpr int kMaxDevices = 64;
-
-// k_evid_steps may ask for more dynamic LDS than a launch gets by default: raised once per process and device, and a
-// refusal is reported as what it is
-int raise_lds_limit(int device) {
-    static std::mutex mu;
-    static bool done[kMaxDevices] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    if (device < kMaxDevices && done[device]) return 0;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_evid_steps), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)kStepsMaxLds);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("vamp_evid_run: this device does not grant a workgroup " + std::to_string(kStepsMaxLds / 1024) +
-                    " KiB of dynamic LDS (hipFuncSetAttribute(MaxDynamicSharedMemorySize): " + hipGetErrorString(e) +
-                    "); the kernels are built for gfx950's 160 KiB");
-    }
-    if (device < kMaxDevices) done[device] = true;
-    return 0;
-}
-
-int lanes_of(int P, int K) { return (VAMP_EVID_NARROW && P <= kNarrowMaxPix && K <= kNarrowMaxK) ? kNarrowLanes : 64; }
-
 // the checks of one region and its host-side record (pointers unset); `at` opens the message
 int check_region(const std::string& at, const double* x, const double* flux, const double* noise, int P, int K, int mode, int sd,
                  const double* bounds, Reg& R) {
@@ -510,7 +413,7 @@ int check_region(const std::string& at, const double* x, const double* flux, con
     }
     R = Reg{};
     R.P = P; R.K = K; R.q = mode == 1 ? 4 : 3; R.sd = sd; R.D = R.q * K + sd;
-    R.lanes = lanes_of(P, K);
+    R.lanes = vamp::group_lanes(VAMP_EVID_NARROW, P, K);
     if (bounds) {
         R.c_lo = bounds[0]; R.c_hi = bounds[1];
         R.w_max = mode == 0 ? bounds[2] : bounds[3];
@@ -551,16 +454,6 @@ int upload_pixels(DevBuf& buf, std::vector<Reg>& regs, const double* const* x, c
         o += R.P;
     }
     HIP_TRY(hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    return 0;
-}
-
-int set_device(const std::string& fn, int device, DeviceRestore& restore) {
-    int ndev = 0, prev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(fn + "no HIP device " + std::to_string(device));
-    HIP_TRY(hipGetDevice(&prev));
-    restore.dev = prev;
-    HIP_TRY(hipSetDevice(device));
     return 0;
 }
 
@@ -666,7 +559,8 @@ VAMP_EVID_API int vamp_evid_run(int device, void* hip_stream, int n_regions, con
 
     DeviceRestore restore;
     if (set_device(fn, device, restore)) return -1;
-    if (lds_max > kDefaultLds && raise_lds_limit(device)) return -1;
+    // k_evid_steps may ask for more dynamic LDS than a launch gets by default
+    if (lds_max > kDefaultLds && raise_lds_limit(fn, device, {{reinterpret_cast<const void*>(&k_evid_steps), kStepsMaxLds}})) return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
 
     DevBuf d_pix, d_regs, d_beta, d_start, d_startp, d_X, d_ll, d_trace, d_cnt, d_out, d_chain, d_swaptr;
@@ -765,22 +659,17 @@ VAMP_EVID_API int vamp_evid_run(int device, void* hip_stream, int n_regions, con
                        d_trace.as<double>(), nacc, nswap, dout + o_z, dout + o_se, dout + o_ti, dout + o_m, dout + o_v, dout + o_ma, dout + o_sa);
     HIP_TRY(hipGetLastError());
 
-    auto fetch = [&](void* dst, const void* src, long long bytes) -> int {
-        if (!dst || bytes == 0) return 0;
-        HIP_TRY(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, st));
-        return 0;
-    };
     const long long sz = sizeof(double);
-    if (fetch(lnZ, dout + o_z, G * sz) || fetch(lnZ_se, dout + o_se, G * sz) || fetch(lnZ_ti, dout + o_ti, G * sz) ||
-        fetch(mean_lnL, dout + o_m, (long long)G * T * sz) || fetch(var_lnL, dout + o_v, (long long)G * T * sz) ||
-        fetch(move_accept, dout + o_ma, (long long)G * T * sz) || fetch(swap_accept, dout + o_sa, (long long)G * (T - 1) * sz) ||
-        fetch(lnl_trace, d_trace.p, trace_len * sz) || fetch(swap_trace, d_swaptr.p, swap_len))
+    if (fetch(lnZ, dout + o_z, G * sz, st) || fetch(lnZ_se, dout + o_se, G * sz, st) || fetch(lnZ_ti, dout + o_ti, G * sz, st) ||
+        fetch(mean_lnL, dout + o_m, (long long)G * T * sz, st) || fetch(var_lnL, dout + o_v, (long long)G * T * sz, st) ||
+        fetch(move_accept, dout + o_ma, (long long)G * T * sz, st) || fetch(swap_accept, dout + o_sa, (long long)G * (T - 1) * sz, st) ||
+        fetch(lnl_trace, d_trace.p, trace_len * sz, st) || fetch(swap_trace, d_swaptr.p, swap_len, st))
         return -1;
     if (!chain_is_device)
         for (int g = 0; g < G; ++g) {
             const Reg& R = regs[g];
-            if (R.chain && fetch(chain[g], R.chain, (long long)n_keep * W * R.D * sz)) return -1;
-            if (R.chain_ll && fetch(chain_lnl[g], R.chain_ll, (long long)n_keep * W * sz)) return -1;
+            if (R.chain && fetch(chain[g], R.chain, (long long)n_keep * W * R.D * sz, st)) return -1;
+            if (R.chain_ll && fetch(chain_lnl[g], R.chain_ll, (long long)n_keep * W * sz, st)) return -1;
         }
     HIP_TRY(hipStreamSynchronize(st));
     return 0;

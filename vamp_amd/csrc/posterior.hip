@@ -20,11 +20,12 @@
 
 #include <cmath>
 #include <cstdint>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/vamp_post.h"
+#include "lane_group.hpp"
+#include "side_call.hpp"
 #include "voigt_math.hpp"
 
 #define VAMP_POST_API extern "C" __attribute__((visibility("default")))
@@ -44,12 +45,14 @@
 
 namespace {
 
+using namespace vamp::side;
+using vamp::lds_fence;
+
 constexpr int kEvalBlock = 256;            // four wavefronts
 constexpr int kEvalWaves = kEvalBlock / 64;
 constexpr int kSamplesPerBlock = 64;
 constexpr int kRec = 6;                    // doubles of a line record
 constexpr int kColBlock = 1024;            // one size for every column: the reduction order must not depend on the pass
-constexpr int kNarrowLanes = 16, kNarrowMaxPix = 32, kNarrowMaxK = 4;
 constexpr long long kDefaultScratch = 256ll << 20;
 constexpr double SQRT_LN2 = 0.83255461115769775635;
 
@@ -66,7 +69,7 @@ struct Item {                      // one (group, pixel range)
     long long ld;                  // stride of t, in doubles
     long long fs_s, fs_p;          // strides of the scratch
     int W, D, K, q;                // q = 3 (Gauss) or 4 (Voigt) parameters per line
-    int S, np, p0, lanes;          // lanes that own a sample: 64 or kNarrowLanes
+    int S, np, p0, lanes;          // lanes that own a sample (vamp::group_lanes)
 };
 
 struct ColSet {                    // columns that share a source matrix
@@ -81,12 +84,10 @@ struct ColSet {                    // columns that share a source matrix
     int S, n2;                     // n2: S rounded up to a power of two
 };
 
-__device__ __forceinline__ void lds_fence() {      // LDS traffic between the lanes of one wavefront
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// The group geometry, the table fill and the optical depth of a line are written out here, not taken from
+// lane_group.hpp: through the header's functions the compiler orders this kernel's loads differently and renumbers
+// its registers (code 8472 -> 8488 bytes; 128 VGPRs, 100 SGPRs, occupancy 4, no scratch either way), and that form has
+// not been timed or compared bit for bit on a device.  eval_point of evidence.hip compiles to the same code both ways.
 __global__ __launch_bounds__(kEvalBlock) void k_post_eval(const Item* __restrict__ items, const int2* __restrict__ tasks,
                                                           int region_doubles) {
     extern __shared__ double lds[];
@@ -177,20 +178,6 @@ __global__ __launch_bounds__(kEvalBlock) void k_post_eval(const Item* __restrict
     }
 }
 
-// sum over the workgroup in a fixed order
-__device__ inline double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int o = kColBlock / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // Dynamic LDS: n2 doubles.
 __global__ __launch_bounds__(kColBlock) void k_post_column(const ColSet* __restrict__ sets, const int2* __restrict__ tasks,
                                                            const double* __restrict__ probs, int Q) {
@@ -213,8 +200,8 @@ __global__ __launch_bounds__(kColBlock) void k_post_column(const ColSet* __restr
         }
         col[i] = v;
     }
-    const int n_bad = (int)block_sum(nb, red);       // (ends with a barrier: the column is staged)
-    const int n_nan = (int)block_sum(nn, red);
+    const int n_bad = (int)vamp::block_sum<kColBlock>(nb, red);       // (ends with a barrier: the column is staged)
+    const int n_nan = (int)vamp::block_sum<kColBlock>(nn, red);
     const int n = C.S - n_bad;
 
     for (int k = 2; k <= n2; k <<= 1)
@@ -231,10 +218,10 @@ __global__ __launch_bounds__(kColBlock) void k_post_column(const ColSet* __restr
 
     double part = 0.0;
     for (int i = tid; i < n; i += kColBlock) part += col[i];
-    const double mean = block_sum(part, red) / (double)n;
+    const double mean = vamp::block_sum<kColBlock>(part, red) / (double)n;
     part = 0.0;
     for (int i = tid; i < n; i += kColBlock) { const double d = col[i] - mean; part = fma(d, d, part); }
-    const double var = block_sum(part, red) / (double)n;
+    const double var = vamp::block_sum<kColBlock>(part, red) / (double)n;
     const bool none = n == 0 || n_nan > 0;           // a NaN among the values makes every statistic NaN, as in numpy
 
     if (tid == 0) {
@@ -257,67 +244,8 @@ __global__ __launch_bounds__(kColBlock) void k_post_column(const ColSet* __restr
     }
 }
 
-thread_local std::string g_err;
-
-int fail(const std::string& msg) {
-    g_err = msg;
-    return -1;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            (void)hipGetLastError();                                                                    \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                             \
-        }                                                                                               \
-    } while (0)
-
-struct DevBuf {                    // released on every exit path
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-struct DeviceRestore {             // the caller's current device, put back on every exit path
-    int dev = -1;
-    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
-};
-
-template <class T>
-int upload(DevBuf& buf, const std::vector<T>& v, hipStream_t st) {
-    if (v.empty()) return 0;
-    HIP_TRY(hipMalloc(&buf.p, v.size() * sizeof(T)));
-    HIP_TRY(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
-    return 0;
-}
-
 constexpr size_t kColMaxLds = (size_t)VAMP_POST_MAX_SAMPLES * sizeof(double);
 constexpr size_t kEvalMaxLds = (size_t)kEvalWaves * slot_doubles(VAMP_POST_MAX_COMPONENTS, 64) * sizeof(double);
-constexpr int kMaxDevices = 64;
-
-// Both kernels may ask for more dynamic LDS than a launch gets by default: raised once per process and device,
-// and a refusal is reported as what it is
-int raise_lds_limits(int device) {
-    static std::mutex mu;
-    static bool done[kMaxDevices] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    if (device < kMaxDevices && done[device]) return 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post_column), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kColMaxLds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post_eval), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kEvalMaxLds);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("vamp_post_summaries: this device does not grant a workgroup " + std::to_string(kColMaxLds / 1024) +
-                    " KiB of dynamic LDS (hipFuncSetAttribute(MaxDynamicSharedMemorySize): " + hipGetErrorString(e) +
-                    "); the kernels are built for gfx950's 160 KiB");
-    }
-    if (device < kMaxDevices) done[device] = true;
-    return 0;
-}
-
 struct Pass {
     size_t item0, item1;           // its items
     size_t etask0, etask1;         // its k_post_eval workgroups
@@ -387,33 +315,20 @@ VAMP_POST_API int vamp_post_summaries(int device, void* hip_stream, int n_groups
                     std::to_string((long long)s_max * (long long)sizeof(double)) + " bytes)");
 
     DeviceRestore restore;
-    int ndev = 0, prev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(fn + "no HIP device " + std::to_string(device));
-    HIP_TRY(hipGetDevice(&prev));
-    restore.dev = prev;
-    HIP_TRY(hipSetDevice(device));
-    if (raise_lds_limits(device)) return -1;
+    if (set_device(fn, device, restore)) return -1;
+    // both kernels may ask for more dynamic LDS than a launch gets by default
+    if (raise_lds_limit(fn, device, {{reinterpret_cast<const void*>(&k_post_column), kColMaxLds},
+                                     {reinterpret_cast<const void*>(&k_post_eval), kEvalMaxLds}}))
+        return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
 
     // device view of every group's chain: staged (host input) or as given
-    std::vector<const double*> dbase(n_groups, nullptr);
+    std::vector<const double*> dbase(base, base + n_groups);
     DevBuf staging;
     if (!is_device) {
-        std::vector<long long> off(n_groups), len(n_groups);
-        long long total = 0;
-        for (int g = 0; g < n_groups; ++g) {
-            off[g] = total;
-            len[g] = (long long)(n_keep[g] - 1) * ld[g] + (long long)walkers[g] * Dg[g];
-            total += len[g];
-        }
-        HIP_TRY(hipMalloc(&staging.p, total * sizeof(double)));
-        for (int g = 0; g < n_groups; ++g) {
-            HIP_TRY(hipMemcpyAsync(staging.as<double>() + off[g], base[g], len[g] * sizeof(double), hipMemcpyHostToDevice, st));
-            dbase[g] = staging.as<double>() + off[g];
-        }
-    } else {
-        for (int g = 0; g < n_groups; ++g) dbase[g] = base[g];
+        std::vector<long long> len(n_groups);
+        for (int g = 0; g < n_groups; ++g) len[g] = chain_span(n_keep[g], ld[g], walkers[g], Dg[g]);
+        if (stage_chains(len, base, st, staging, dbase)) return -1;
     }
 
     // one buffer of doubles: abscissae | decrement sums | outputs; one of bytes (bad flags); one of counts
@@ -459,7 +374,7 @@ VAMP_POST_API int vamp_post_summaries(int device, void* hip_stream, int n_groups
             const int S = Sg[g], K = n_comp[g], P = n_pix[g];
             int n2 = 1;
             while (n2 < S) n2 <<= 1;
-            const int lanes = (VAMP_POST_NARROW && P <= kNarrowMaxPix && K <= kNarrowMaxK) ? kNarrowLanes : 64;
+            const int lanes = vamp::group_lanes(VAMP_POST_NARROW, P, K);
             const int region = (64 / lanes) * slot_doubles(K, lanes);
             double* ew = dm + o_ew + ew_off;
             uint8_t* bad = d_bad.as<uint8_t>() + s_off;
@@ -538,14 +453,12 @@ VAMP_POST_API int vamp_post_summaries(int device, void* hip_stream, int n_groups
         HIP_TRY(hipGetLastError());
     }
 
-    auto fetch = [&](double* dst, long long off, long long n) -> int {
-        if (!dst || n == 0) return 0;
-        HIP_TRY(hipMemcpyAsync(dst, dm + off, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        return 0;
-    };
-    if (fetch(flux_mean, o_fm, tot_pix) || fetch(flux_sd, o_fs, tot_pix) || fetch(flux_q, o_fq, tot_pix * Q) ||
-        fetch(ew_mean, o_em, n_groups) || fetch(ew_sd, o_es, n_groups) || fetch(ew_q, o_eq, (long long)n_groups * Q) ||
-        fetch(comp_ew_mean, o_cm, tot_comp) || fetch(comp_ew_sd, o_cs, tot_comp) || fetch(comp_ew_q, o_cq, tot_comp * Q))
+    const long long sz = sizeof(double);
+    if (fetch(flux_mean, dm + o_fm, tot_pix * sz, st) || fetch(flux_sd, dm + o_fs, tot_pix * sz, st) ||
+        fetch(flux_q, dm + o_fq, tot_pix * Q * sz, st) || fetch(ew_mean, dm + o_em, n_groups * sz, st) ||
+        fetch(ew_sd, dm + o_es, n_groups * sz, st) || fetch(ew_q, dm + o_eq, (long long)n_groups * Q * sz, st) ||
+        fetch(comp_ew_mean, dm + o_cm, tot_comp * sz, st) || fetch(comp_ew_sd, dm + o_cs, tot_comp * sz, st) ||
+        fetch(comp_ew_q, dm + o_cq, tot_comp * Q * sz, st))
         return -1;
     std::vector<int32_t> counts((size_t)n_groups * 2);
     HIP_TRY(hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));

@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _diag_lib
+from ._sidelib import fits_with_chain, region_bases
 
 MAX_SAMPLES = 8192            # VAMP_DIAG_MAX_SAMPLES of include/vamp_diag.h
 
@@ -92,10 +93,8 @@ def context_diagnostics(ctx, chain_ptr, n_keep, c=5.0, thin=1):
     context's device (default stream, after the context's stream is synchronised)."""
     ctx.synchronize()                  # the sampler's stream is done with the chain before the default stream reads it
     W, ndims = int(ctx.W), list(ctx.ndims)
-    offs = np.concatenate([[0], np.cumsum([W * d for d in ndims])]).astype(np.int64)
-    bases = [int(chain_ptr) + 8 * int(o) for o in offs[:-1]]
     R = len(ndims)
-    flat = _call(ctx.device, bases, True, [ctx.total_theta] * R, [int(n_keep)] * R, [W] * R, ndims, float(c))
+    flat = _call(ctx.device, region_bases(ctx, chain_ptr), True, [ctx.total_theta] * R, [int(n_keep)] * R, [W] * R, ndims, float(c))
     return _split(flat, ndims, [int(thin)] * R)
 
 
@@ -104,8 +103,7 @@ def fits_diagnostics(fits, c=5.0, device=0):
     cache is filled from it.  Fits without a chain are left out; so are chains of more than MAX_SAMPLES kept samples,
     which the library rejects (a long run, e.g. ``--iterations 10000 --thin 1``, must still get its perf record).
     Returns (records of the fits diagnosed, number of fits left out for their length)."""
-    have = [f for f in fits if getattr(getattr(f, "mcmc", None), "_fit", None) is not None
-            and getattr(f, "_chain_dev", None) is not None]
+    have = fits_with_chain(fits)
     ok = [f for f in have if f._chain_dev.shape[0] <= MAX_SAMPLES]
     skipped = len(have) - len(ok)
     if not ok:

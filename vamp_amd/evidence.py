@@ -17,10 +17,10 @@ import ctypes as C
 import numpy as np
 
 from . import _evid_lib
+from ._sidelib import Q_OF_MODE
 
 MAX_COMPONENTS, MAX_WALKERS, MAX_TEMPS = 8, 256, 64      # of include/vamp_evid.h
 DEFAULT_SEED = 20110101
-_Q_OF_MODE = {0: 3, 1: 4}
 _DP, _IP = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 
 
@@ -73,7 +73,7 @@ def lnlike(region, theta, device=0):
     """(ln L, ln pi) of the rows of ``theta`` [n, D] by the device function the sampler uses"""
     sp = _spec(region, 0)
     theta = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
-    D = _Q_OF_MODE.get(sp["mode"], 3) * sp["n_comp"] + int(sp["sample_sd"])
+    D = Q_OF_MODE.get(sp["mode"], 3) * sp["n_comp"] + int(sp["sample_sd"])
     if theta.shape[1] != D:
         raise ValueError(f"theta has {theta.shape[1]} parameters per row, the region {D}")
     ll, lp = np.empty(theta.shape[0]), np.empty(theta.shape[0])
@@ -98,7 +98,7 @@ def _run(specs, betas, walkers, steps, burn, swap_every, seed, a, starts, device
     out = {k: np.empty(n) for k, n in (("lnZ", G), ("lnZ_se", G), ("lnZ_ti", G), ("mean_lnL", G * T), ("var_lnL", G * T),
                                        ("move_accept", G * T), ("swap_accept", G * (T - 1)))}
     ok = n_keep > 0 and 0 < W <= MAX_WALKERS and 0 < T <= MAX_TEMPS        # (the library refuses the rest; no big allocation for it)
-    dims = [_Q_OF_MODE.get(s["mode"], 3) * s["n_comp"] + int(s["sample_sd"]) for s in specs]
+    dims = [Q_OF_MODE.get(s["mode"], 3) * s["n_comp"] + int(s["sample_sd"]) for s in specs]
     chains = [np.empty((n_keep, W, D)) if want_chain and ok else None for D in dims]
     chain_ll = [np.empty((n_keep, W)) if want_chain and ok else None for _ in specs]
     trace = np.empty((G, n_keep, T, W)) if want_trace and ok else None
@@ -138,7 +138,7 @@ def log_evidence(regions, n_temps=16, walkers=32, steps=600, burn=200, swap_ever
     if start is not None and len(start) != len(specs):
         raise ValueError("one start block (or None) per region is required")
     for sp, s in zip(specs, start or []):
-        D = _Q_OF_MODE.get(sp["mode"], 3) * sp["n_comp"] + int(sp["sample_sd"])
+        D = Q_OF_MODE.get(sp["mode"], 3) * sp["n_comp"] + int(sp["sample_sd"])
         if s is not None and np.shape(s) != (int(walkers), D):
             raise ValueError(f"a start block must be [walkers, D] = [{int(walkers)}, {D}]")
     if betas is None:

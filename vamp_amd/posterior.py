@@ -17,11 +17,11 @@ import ctypes as C
 import numpy as np
 
 from . import _post_lib
+from ._sidelib import Q_OF_MODE, fits_with_chain, region_bases
 
 MAX_SAMPLES = 16384           # VAMP_POST_MAX_SAMPLES of include/vamp_post.h
 MAX_PROBS = 16
 DEFAULT_PROBS = (0.025, 0.16, 0.5, 0.84, 0.975)
-_Q_OF_MODE = {0: 3, 1: 4}
 
 _FLAT = ("flux_mean", "flux_sd", "flux_q", "ew_mean", "ew_sd", "ew_q", "comp_ew_mean", "comp_ew_sd", "comp_ew_q", "n_used", "n_bad")
 
@@ -137,7 +137,7 @@ def posterior_summaries(xs, chains, n_comp, mode, sample_sd=False, probs=DEFAULT
     n_comp, modes, sds = _per_group(n_comp, G, int), _per_group(mode, G, int), _per_group(sample_sd, G, lambda v: int(bool(v)))
     widths, steps = _per_group(pixel_width, G, float), _per_group(steps, G, int)
     for a, k, m, sd in zip(arrays, n_comp, modes, sds):
-        if m in _Q_OF_MODE and a.shape[2] != _Q_OF_MODE[m] * k + sd:
+        if m in Q_OF_MODE and a.shape[2] != Q_OF_MODE[m] * k + sd:
             raise ValueError(f"a chain of {a.shape[2]} parameters does not hold {k} lines of mode {m} (sample_sd = {sd})")
     probs = _probs(probs)
     flat = _post_host(xs, arrays, n_comp, modes, sds, widths, probs, steps, int(device), int(scratch_bytes))
@@ -158,11 +158,9 @@ def context_posterior(ctx, chain_ptr, n_keep, xs, probs=DEFAULT_PROBS, pixel_wid
         raise ValueError("one abscissa per region of the context is required")
     mode = int(ctx.mode)
     ks = [int(k) for k in ctx.n_comp]
-    sds = [d - _Q_OF_MODE.get(mode, 3) * k for d, k in zip(ndims, ks)]
-    offs = np.concatenate([[0], np.cumsum([W * d for d in ndims])]).astype(np.int64)
-    bases = [int(chain_ptr) + 8 * int(o) for o in offs[:-1]]
+    sds = [d - Q_OF_MODE.get(mode, 3) * k for d, k in zip(ndims, ks)]
     probs = _probs(probs)
-    flat = _call(ctx.device, xs, ks, [mode] * R, sds, bases, True, [ctx.total_theta] * R, [int(n_keep)] * R, [W] * R,
+    flat = _call(ctx.device, xs, ks, [mode] * R, sds, region_bases(ctx, chain_ptr), True, [ctx.total_theta] * R, [int(n_keep)] * R, [W] * R,
                  _per_group(pixel_width, R, float), probs, scratch_bytes)
     return _split(flat, [len(x) for x in xs], ks, probs, [1] * R)
 
@@ -172,8 +170,7 @@ def fits_posterior(fits, probs=DEFAULT_PROBS, pixel_width=1.0, device=0, scratch
     ``fit._x``); each fit's ``mcmc.flux_band()`` / ``mcmc.equivalent_widths()`` cache is filled from it when
     ``pixel_width`` is 1.  A chain of more than MAX_SAMPLES samples is read at the smallest time step that fits; the
     step is each record's ``step``.  Fits without a chain are left out.  Returns (fits summarised, their records)."""
-    have = [f for f in fits if getattr(getattr(f, "mcmc", None), "_fit", None) is not None
-            and getattr(f, "_chain_dev", None) is not None]
+    have = fits_with_chain(fits)
     if not have:
         return [], []
     steps = [time_step(f._chain_dev.shape[0], f._chain_dev.shape[1]) for f in have]
