@@ -13,12 +13,16 @@
  * Output, per (group, parameter), in group order (sum of ndim entries, host arrays):
  *   tau      integrated autocorrelation time, in kept samples (+inf: a walker's series is constant)
  *   n_eff    N * W / tau (NaN when tau <= 0)
- *   r_hat    split-R-hat (BDA3, not rank-normalised)
+ *   r_hat    split-R-hat (BDA3, not rank-normalised); NaN under the rule for values that are not finite, below
  *   window   the window M the sum of tau stops at (-1 when tau is +inf or NaN)
  *   reliable 1 when a window was found, tau > 0 and N >= 50 max(tau, 1): never for N < 50.  (tau_{N-1} = 0
  *            identically -- the centred series' autocovariances sum to zero -- so on a very short chain the window
  *            can land where tau_m has collapsed to about 0 or below; such a tau is reported but never trusted.)
  * A group with N < 4 gets NaN everywhere (window -1, reliable 0); it is not an error.
+ * Values that are not finite: a NaN or +-inf anywhere in the series of any walker of a (group, parameter) gives
+ * tau = n_eff = r_hat = NaN, window = -1 and reliable = 0 for that parameter.  This comes before "a walker's series
+ * is constant" (a series that is constant but for a NaN is not finite, not stuck).  The other parameters of the
+ * group are not affected.
  *
  * Every function returns 0 on success and -1 on an error; vamp_diag_last_error() then says why.
  * The caller's current HIP device is restored before return.

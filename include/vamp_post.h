@@ -21,7 +21,11 @@
  * (sums in pixel order).  A sample is BAD when one of its q K parameters is not finite, or sigma <= 0, or
  * G_fwhm <= 0, or L_fwhm < 0; bad samples are left out of every statistic and counted.  Over the n = S - n_bad others:
  * the mean, the population standard deviation about the mean, and numpy's default ("linear") quantiles of the
- * exact order statistics.  n = 0: every statistic is NaN; it is not an error.
+ * exact order statistics.  n = 0: every statistic is NaN; it is not an error.  A good sample's value may still be
+ * NaN or infinite (an overflowing amplitude): a NaN among the n values of a column makes every statistic of that
+ * column NaN, and an infinite value is treated as numpy treats it -- the mean is infinite, the standard deviation
+ * NaN, and a quantile whose interpolation touches the infinite order statistic with weight 0 is NaN (inf - inf),
+ * also at p = 0 and p = 1.
  *
  * Output, host arrays in group order; any pointer may be NULL:
  *   flux_mean, flux_sd      sum of n_pix doubles

@@ -14,7 +14,9 @@ def _autocov(y):
 
 
 def diagnostics(chain, c=5.0):
-    """chain [N, W, D] -> (tau, n_eff, r_hat, window, reliable), arrays of length D"""
+    """chain [N, W, D] -> (tau, n_eff, r_hat, window, reliable), arrays of length D.  A NaN or +-inf anywhere in the series
+    of any walker of a parameter gives tau = n_eff = r_hat = NaN, window = -1 and reliable = False for that parameter alone;
+    this comes before "a walker's series is constant" (include/vamp_diag.h)"""
     chain = np.asarray(chain, dtype=np.float64)
     N, W, D = chain.shape
     tau, n_eff, r_hat = np.full(D, np.nan), np.full(D, np.nan), np.full(D, np.nan)
@@ -24,6 +26,8 @@ def diagnostics(chain, c=5.0):
     n = N // 2
     for d in range(D):
         x = chain[:, :, d]
+        if not np.isfinite(x).all():                         # a NaN or an infinity in any walker's series: NaN, window -1,
+            continue                                         # not reliable; this comes before "stuck"
         stuck = np.ptp(x, axis=0) == 0                       # c_w(0) = 0: a constant series
         # split-R-hat (BDA3, no rank normalisation); a constant walker's halves have mean x_0 and variance 0
         seq = np.concatenate([x[:n], x[N - n:]], axis=1)     # [n, 2W]
@@ -47,7 +51,7 @@ def diagnostics(chain, c=5.0):
         ok = np.arange(N) >= c * taus
         found = bool(ok.any())
         M = int(np.argmax(ok)) if found else N - 1
-        tau[d], window[d] = taus[M], M
+        tau[d], window[d] = taus[M], (M if not np.isnan(taus[M]) else -1)
         n_eff[d] = N * W / taus[M] if taus[M] > 0 else np.nan
         reliable[d] = found and taus[M] > 0 and N >= 50.0 * max(taus[M], 1.0)
     return tau, n_eff, r_hat, window, reliable

@@ -44,6 +44,28 @@ def test_stuck_walker():
     assert ref.diagnostics(x)[2][0] == np.inf
 
 
+def test_values_that_are_not_finite():
+    """a NaN or an infinity anywhere in a parameter's series: tau = n_eff = r_hat = NaN, window -1, not reliable, for that
+    parameter alone; the rule comes before "stuck" (a series that is constant but for a NaN is not finite, not stuck)"""
+    rng = np.random.default_rng(16)
+    clean = ref.ar1(rng, 300, 16, 5, 0.5)
+    x = clean.copy()
+    x[100, 3, 0] = np.nan
+    x[299, 15, 1] = np.inf
+    x[:, 5, 2] = 0.1
+    x[0, 5, 2] = np.nan                # constant but for a NaN
+    x[:, 6, 3] = 0.1                   # stuck, and finite
+    x[17, 2, 3] = -np.inf              # ... beside an infinity in another walker: not finite comes first
+    tau, n_eff, r_hat, window, reliable = ref.diagnostics(x)
+    for a in (tau, n_eff, r_hat):
+        assert np.all(np.isnan(a[:4]))
+    assert np.all(window[:4] == -1) and not reliable[:4].any()
+    want = ref.diagnostics(clean)
+    for got, w in zip((tau, n_eff, r_hat, window, reliable), want):
+        assert got[4] == w[4]
+    assert np.isfinite(tau[4]) and window[4] > 0 and reliable[4]
+
+
 def test_collapsed_tau_of_a_very_short_chain_is_never_reliable():
     """tau_{N-1} = 0 identically: white noise of N = 5 puts the window where tau_m has collapsed below 0; that tau is
     reported, but n_eff is not negative and the result is not reliable"""

@@ -7,10 +7,12 @@
 //                   split-half means and variances; then the direct lag sums c_w(k), k = 0..N-1, register
 //                   blocked R lags per lane (a ring of y_{t+k0 .. t+k0+R-1}: two LDS reads per R FMAs),
 //                   normalised by c_w(0) and summed over the chunk's walkers -> rho_part[pair][chunk][k];
-//                   the chunk's R-hat partials -> stat_part[pair][chunk][5].
+//                   the chunk's R-hat partials, its stuck walkers and its walkers that hold a NaN or an
+//                   infinity -> stat_part[pair][chunk][6].
 //   k_chain_finish  one workgroup per (group, parameter): sums the chunks, rho_bar = sum / W, prefix sum of
 //                   rho_bar by wavefront shuffles until the window m >= c tau_m is found, Chan's combination
-//                   of the chunks' sequence means for R-hat.
+//                   of the chunks' sequence means for R-hat.  A series with a value that is not finite in any
+//                   walker is answered NaN (window -1, not reliable), before "stuck" is looked at.
 // Everything is fp64.
 #include <hip/hip_runtime.h>
 
@@ -30,7 +32,8 @@ namespace {
 
 using namespace vamp::side;
 
-constexpr int kStats = 5;          // per chunk: sequences, mean of their means, M2 of their means, sum of s^2, stuck walkers
+constexpr int kStats = 6;          // per chunk: sequences, mean of their means, M2 of their means, sum of s^2, stuck walkers,
+                                   // walkers with a value that is not finite
 constexpr int kMaxWc = 64;         // walkers per chunk at most
 constexpr int kSmallN = 2048;      // N <= kSmallN: R = 8 lags per lane, 256 threads; else R = 16, 512 threads
 constexpr int kTileSmall = 4096;   // LDS tile budget in doubles, small-N path (32 KiB: several workgroups per CU)
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(BLOCK) void k_chain_lags(const Pair* __restrict__ p
     extern __shared__ double tile[];
     __shared__ double red[5][BLOCK];
     __shared__ double w_mean[kMaxWc], w_h1[kMaxWc], w_h2[kMaxWc], w_v1[kMaxWc], w_v2[kMaxWc], w_inv[kMaxWc];
-    __shared__ int w_stuck[kMaxWc];
+    __shared__ int w_flag[kMaxWc];                // 1: stuck (a constant series); 2: holds a NaN or an infinity
 
     const int2 task = tasks[blockIdx.x];
     const Pair p = pairs[task.x];
@@ -72,7 +75,8 @@ __global__ __launch_bounds__(BLOCK) void k_chain_lags(const Pair* __restrict__ p
     }
     __syncthreads();
 
-    // 2. per walker: sums of the whole series and of both halves, range (P threads per walker)
+    // 2. per walker: sums of the whole series and of both halves, range (P threads per walker).  fmin / fmax skip a
+    //    NaN, so a value that is not finite opens the range to (-inf, +inf): no finite series has that range
     const int P = BLOCK / Wc;
     const int w = tid % Wc, part = tid / Wc;
     const bool act = part < P && w < wn;
@@ -86,6 +90,7 @@ __global__ __launch_bounds__(BLOCK) void k_chain_lags(const Pair* __restrict__ p
                 if (t >= N - n) s2 += x;
                 lo = fmin(lo, x);
                 hi = fmax(hi, x);
+                if (!(fabs(x) < INFINITY)) { lo = -INFINITY; hi = INFINITY; }
             }
         }
         red[0][tid] = s; red[1][tid] = s1; red[2][tid] = s2; red[3][tid] = lo; red[4][tid] = hi;
@@ -98,9 +103,10 @@ __global__ __launch_bounds__(BLOCK) void k_chain_lags(const Pair* __restrict__ p
             s += red[0][j]; s1 += red[1][j]; s2 += red[2][j];
             lo = fmin(lo, red[3][j]); hi = fmax(hi, red[4][j]);
         }
-        const bool stuck = !(hi > lo);            // a constant series: c_w(0) = 0
-        const double x0 = tile[tid];
-        w_stuck[tid] = stuck ? 1 : 0;
+        const bool finite = lo > -INFINITY && hi < INFINITY;
+        const bool stuck = !finite || !(hi > lo); // a constant series: c_w(0) = 0 (a series that is not finite takes the
+        const double x0 = tile[tid];              // same arithmetic; k_chain_finish answers its parameter NaN)
+        w_flag[tid] = !finite ? 2 : stuck ? 1 : 0;
         w_mean[tid] = stuck ? x0 : s / N;
         w_h1[tid] = stuck ? x0 : s1 / n;
         w_h2[tid] = stuck ? x0 : s2 / n;
@@ -130,7 +136,7 @@ __global__ __launch_bounds__(BLOCK) void k_chain_lags(const Pair* __restrict__ p
             const int j = q * Wc + tid;
             c0 += red[0][j]; q1 += red[1][j]; q2 += red[2][j];
         }
-        const bool stuck = w_stuck[tid] != 0;
+        const bool stuck = w_flag[tid] != 0;
         w_inv[tid] = stuck ? 0.0 : 1.0 / c0;
         w_v1[tid] = stuck ? 0.0 : q1 / (n - 1);
         w_v2[tid] = stuck ? 0.0 : q2 / (n - 1);
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(BLOCK) void k_chain_lags(const Pair* __restrict__ p
 
     // 4. the chunk's R-hat partials: Welford over its 2 wn sequence means (one lane; wn <= 64)
     if (tid == 0) {
-        double cnt = 0.0, mean = 0.0, m2 = 0.0, ssq = 0.0, stuck = 0.0;
+        double cnt = 0.0, mean = 0.0, m2 = 0.0, ssq = 0.0, stuck = 0.0, nonfin = 0.0;
         for (int j = 0; j < wn; ++j) {
             const double hs[2] = {w_h1[j], w_h2[j]};
             for (int h = 0; h < 2; ++h) {
@@ -149,10 +155,11 @@ __global__ __launch_bounds__(BLOCK) void k_chain_lags(const Pair* __restrict__ p
                 m2 = fma(d, hs[h] - mean, m2);
             }
             ssq += w_v1[j] + w_v2[j];
-            stuck += w_stuck[j];
+            stuck += w_flag[j] & 1;
+            nonfin += w_flag[j] >> 1;
         }
         double* st = stat_part + p.stat_off + (long long)task.y * kStats;
-        st[0] = cnt; st[1] = mean; st[2] = m2; st[3] = ssq; st[4] = stuck;
+        st[0] = cnt; st[1] = mean; st[2] = m2; st[3] = ssq; st[4] = stuck; st[5] = nonfin;
     }
 
     // 5. lag sums: lane (s, kb) takes lags kb*R .. kb*R+R-1 of the walkers s, s+S, ... of the chunk
@@ -261,20 +268,23 @@ __global__ __launch_bounds__(256) void k_chain_finish(const Pair* __restrict__ p
         if (done) break;
     }
     if (wv != 0) return;
-    double cnt = 0.0, mean = 0.0, m2 = 0.0, ssq = 0.0, stuck = 0.0;
+    double cnt = 0.0, mean = 0.0, m2 = 0.0, ssq = 0.0, stuck = 0.0, nonfin = 0.0;
     for (int ch = lane; ch < C; ch += 64) {
         const double* st = stat_part + p.stat_off + (long long)ch * kStats;
         chan_combine(cnt, mean, m2, st[0], st[1], st[2]);
         ssq += st[3];
         stuck += st[4];
+        nonfin += st[5];
     }
     for (int o = 32; o >= 1; o >>= 1) {
         const double cb = __shfl_down(cnt, o, 64), mb = __shfl_down(mean, o, 64), m2b = __shfl_down(m2, o, 64);
         const double sb = __shfl_down(ssq, o, 64), kb = __shfl_down(stuck, o, 64);
+        const double fb = __shfl_down(nonfin, o, 64);
         if (lane + o < 64) {
             chan_combine(cnt, mean, m2, cb, mb, m2b);
             ssq += sb;
             stuck += kb;
+            nonfin += fb;
         }
     }
     if (lane != 0) return;
@@ -286,14 +296,16 @@ __global__ __launch_bounds__(256) void k_chain_finish(const Pair* __restrict__ p
     else rh = B > 0.0 ? INFINITY : NAN;
     const int o = p.out;
     r_hat[o] = rh;
-    if (stuck > 0.0) {
+    if (nonfin > 0.0) {                            // a NaN or an infinity in the series of any walker: before "stuck"
+        tau[o] = NAN; n_eff[o] = NAN; r_hat[o] = NAN; window[o] = -1; reliable[o] = 0;
+    } else if (stuck > 0.0) {
         tau[o] = INFINITY; n_eff[o] = 0.0; window[o] = -1; reliable[o] = 0;
     } else {
         // tau_{N-1} = 0 identically, so on a chain too short to have a window tau_M can collapse to ~0 or below:
         // n_eff is NaN for tau <= 0, and reliable needs tau > 0 and N >= 50 max(tau, 1) (so N >= 50 at least)
         tau[o] = tauM;
         n_eff[o] = tauM > 0.0 ? (double)N * Wd / tauM : NAN;
-        window[o] = M;
+        window[o] = tauM == tauM ? M : -1;
         reliable[o] = (found && tauM > 0.0 && (double)N >= 50.0 * fmax(tauM, 1.0)) ? 1 : 0;
     }
 }

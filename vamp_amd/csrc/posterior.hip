@@ -232,13 +232,18 @@ __global__ __launch_bounds__(kColBlock) void k_post_column(const ColSet* __restr
     if (tid < Q) {
         double v = NAN;
         if (!none) {
+            // numpy's arithmetic, one rounding per operation.  Fused, t = fma(n - 1, p, -lo) keeps the unrounded product:
+            // at n = 21, p = 0.975 that is 0.5 - 4e-16 where numpy has 0.5, which picks the other form of the interpolation
+            // below -- +inf where numpy has NaN when the upper order statistic is infinite
+#pragma clang fp contract(off)
             const double h = (double)(n - 1) * probs[tid];
             int lo = (int)floor(h);
             lo = lo < n - 1 ? lo : n - 1;
             const int hi = lo + 1 < n ? lo + 1 : n - 1;
             const double a = col[lo], b = col[hi], t = h - (double)lo, d = b - a;
-            v = t >= 0.5 ? b - d * (1.0 - t) : a + d * t;        // numpy's _lerp
-            if (lo == hi) v = a;
+            // numpy's _lerp, with no shortcut for lo == hi (p = 1, n = 1): an infinite order statistic that is hit
+            // exactly gives inf - inf = NaN there, and so it does here
+            v = t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
         }
         C.q[(long long)tid * C.q_qs + (long long)c * C.q_cs] = v;
     }
