@@ -4,6 +4,9 @@
   python tools/variants.py build NAME=-DFLAG[,-DFLAG2] ...     (here; cross-compiles, no GPU)
   python tools/variants.py run [steps] [extra bench args...]    (on the GPU box; interleaved rounds)
   python tools/variants.py runc3 [steps] [extra args...]         (the same on tools/bench_c3.py, config 3)
+
+Switches of the far-field tile loop that have a build of their own (see the #ifndef block at the top of vamp_hip.hip):
+  mom0=-DVAMP_TILE_MOMENTS=0     every tile pixel by pixel (default 1: tiles without a near line from the data moments)
 """
 import json
 import os

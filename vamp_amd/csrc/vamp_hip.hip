@@ -49,6 +49,7 @@
 #include "map_search.hpp"
 #include "voigt_math.hpp"
 #include "ff_predicates.hpp"
+#include "ff_moments.hpp"
 
 #ifndef VAMP_EARLY_LOADS
 #define VAMP_EARLY_LOADS 1
@@ -111,6 +112,9 @@
 #ifndef VAMP_F32_LEAN_STAGE
 #define VAMP_F32_LEAN_STAGE 1
 #endif
+#ifndef VAMP_TILE_MOMENTS
+#define VAMP_TILE_MOMENTS 1    // fp64 far-field loop: chi^2 of a tile without a near line from the context's data moments (ff_moments.hpp);
+#endif                         // 0: every tile pixel by pixel
 namespace {
 
 constexpr int KMAX = 16;                       // lines per region of the fast shapes (far field, Taylor tables, packing)
@@ -338,6 +342,28 @@ __device__ __forceinline__ double wave_sum(double v) {      // sum over the LPW 
 #pragma unroll
     for (int off = LPW / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// largest value of the 16 lanes of a lane's row, on every lane of the row: row rotations in the data path (DPP), no lane
+// addresses in registers -- for use inside the tile loop, which has none to spare
+template <int N>
+__device__ __forceinline__ double row_ror(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x120 + N, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x120 + N, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// the lane's index in its wavefront, computed where it is called (two instructions the compiler neither hoists nor
+// keeps): for a loop that may hold nothing a lane derives from its index across its iterations
+__device__ __forceinline__ int lane_here() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+__device__ __forceinline__ double row16_max(double v) {
+    v = fmax(v, row_ror<8>(v));
+    v = fmax(v, row_ror<4>(v));
+    v = fmax(v, row_ror<2>(v));
+    return fmax(v, row_ror<1>(v));
 }
 
 // vpfits.py:239-244: -inf for v < 0, else log(v*exp(-v)).  For v <= 700 that is log(v) - v to an
@@ -901,6 +927,9 @@ __device__ __forceinline__ void ff_classify_batch(const LDS& L, TileScratch& Sx,
     const unsigned far16 = ff_tile_field(farmasks, lane), deep16 = ff_tile_field(__ballot(my_deep), lane);
     const unsigned ahead = my_deep ? (deep16 & below) : (deep16 | (far16 & below));
     if (my_far) Sx.farlist[j][__builtin_popcount(ahead)] = (unsigned char)k;
+    // INVARIANT the tile loop relies on (sweep_range_ff, the mark of a tile done from its moments): no line is ever listed
+    // as far AND wide for one tile -- my_wide carries `& !my_far`, and widemasks is zero without WIDE -- so a field with
+    // bits set in BOTH masks cannot come from here.  Whoever changes that must give the mark another place.
     widemasks = 0ull;
     if constexpr (WIDE) {
         const bool my_wide = ((((wide_all >> k) & 1u) != 0u) | (VAMP_MID_NODES && (my_beyond & (dist >= my_wmid)))) & !my_far;
@@ -932,9 +961,12 @@ __device__ __forceinline__ void ff_series(TileScratch& Sx, const double* __restr
 }
 // (b) optical depth of the far lines at the tile's Chebyshev nodes -> the tile's local power series in Sx.coef
 //     (fp32 contexts: ff32_coefficients below, 8 nodes)
+//     ff_node_sums: the node stage alone -- every lane ends with the sum of its node (lane & 15)
 template <class LDS, bool GUARD = true>
-__device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, const unsigned char* farlist, const double* __restrict__ dct,
-                                                int lane, int nfar, double mid, double half, double fs_wide = 0.0) {
+__device__ __forceinline__ double ff_node_sums(const LDS& L, const unsigned char* farlist, const double* __restrict__ dct,
+                                               int lane_, int nfar, double mid, double half, double fs_wide = 0.0) {
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));      // (as in ff_classify_batch: node and group are derived per tile, not kept in registers)
     const int node = lane & (FF_NODES - 1), grp = lane >> 4;
     const double tnode = dct[FF_MAT + node];                       // cos(pi (node + 1/2) / 16)
     __builtin_amdgcn_wave_barrier();
@@ -964,9 +996,45 @@ __device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, c
         fs += fma(an[2], Hb[0], an[3] * Hb[1]);
     }
     fs += fs_wide;
-    fs += __shfl_xor(fs, 16, 64);
-    fs += __shfl_xor(fs, 32, 64);
-    ff_series<double>(Sx, dct, lane, fs);
+    // the sums of the four slot groups: the partners' addresses from the opaque lane index, per tile -- __shfl_xor keeps
+    // them in two registers for the whole loop, which k_lnprob's loop does not have (it reloaded them from scratch)
+    fs += __hiloint2double(__builtin_amdgcn_ds_bpermute((lane ^ 16) << 2, __double2hiint(fs)),
+                           __builtin_amdgcn_ds_bpermute((lane ^ 16) << 2, __double2loint(fs)));
+    fs += __hiloint2double(__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __double2hiint(fs)),
+                           __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __double2loint(fs)));
+    return fs;
+}
+template <class LDS, bool GUARD = true>
+__device__ __forceinline__ void ff_coefficients(const LDS& L, TileScratch& Sx, const unsigned char* farlist, const double* __restrict__ dct,
+                                                int lane, int nfar, double mid, double half, double fs_wide = 0.0) {
+    ff_series<double>(Sx, dct, lane, ff_node_sums<LDS, GUARD>(L, farlist, dct, lane, nfar, mid, half, fs_wide));
+}
+// (d) chi^2 of a tile whose optical depth is the interpolant alone, from the context's data moments `mt` of the tile
+//     (ff_moments.hpp) instead of its pixels.  `a`: the absorption 1 - e^{-tau} at the lane's node, from the node sums.
+//     ff_series turns it into the four series b_q of the absorption; lane 14 q + j < 56 then adds its share
+//     b_q[j] (sum_l b_q[l] Q_q[j + l] + 2 S_q[j]) of C0 + 2 b.S + b'Qb and lane 56 adds C0.  Written on (f - 1, a)
+//     rather than (f, m) the form cancels mildly where the model fits; how mildly is the guard's business (the caller's).
+__device__ __forceinline__ void ff_moment_chi(TileScratch& Sx, const double* __restrict__ dct, const double* __restrict__ mt, int lane,
+                                              double a, double& chi) {
+    const int row = lane < FF_ROWS ? lane : FF_ROWS - 1;
+    const int q = row / (FF_DEG + 1), j = row - q * (FF_DEG + 1);
+    ff_series<double>(Sx, dct, lane, a);
+    // (requested after the transform, whose own loads fill the registers: ahead of it the window costs the loop spills)
+    const double* Qw = mt + q * vamp::FFM_QROW + j;          // Q_q[j .. j + 13]: a contiguous window per lane
+    double Qv[FF_DEG + 1];
+#pragma unroll
+    for (int l = 0; l <= FF_DEG; ++l) Qv[l] = Qw[l];
+    const double Sv = mt[vamp::FFM_S + row], c0 = mt[vamp::FFM_C0];
+    const double* bq = Sx.coef + q * (FF_DEG + 1);
+    double acc0 = Sv + Sv, acc1 = 0.0;
+#pragma unroll
+    for (int l = 0; l <= FF_DEG; l += 2) {
+        acc0 = fma(bq[l], Qv[l], acc0);
+        acc1 = fma(bq[l + 1], Qv[l + 1], acc1);
+    }
+    const double term = Sx.coef[row] * (acc0 + acc1);
+    chi += lane < FF_ROWS ? term : lane == FF_ROWS ? c0 : 0.0;
+    __builtin_amdgcn_wave_barrier();
 }
 // ---- lines far wider than the tile -------------------------------------------------------------------------------
 // An ensemble drawn from the priors (widths ~ U(0, fwhm_max): where every find_bic repeat STARTS, vpfits.py:283-297) has
@@ -1035,7 +1103,8 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
                                                const double* __restrict__ x, const double* __restrict__ f,
                                                const double* __restrict__ wt, const double* __restrict__ ut,
                                                const double2* __restrict__ geo, int lane, int base0, int base1, int stride,
-                                               double& chi, const double* tab, unsigned long long wide_all = 0ull) {
+                                               double& chi, const double* tab, unsigned long long wide_all = 0ull,
+                                               const double* __restrict__ mom = nullptr) {
     constexpr int T = TPIX;
     static_assert(PK::LPW == 64 && PK::KCAP <= 16, "far-field tiles: one walker per wavefront, <= 16 lines");
     const int K = R.K;
@@ -1054,6 +1123,47 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
     for (int batch = base0; batch < base1; batch += FF_BATCH * stride) {
     unsigned long long farmasks, widemasks, zonemasks;
     ff_classify_batch<WIDE, false, TAB>(L, Sx, geo, K, lane, batch, base1, stride, (unsigned)wide_all, farmasks, widemasks, zonemasks);
+    // Tiles without a near line, in a loop of their own ahead of the others' (compiled into the one loop the branch costs
+    // every tile registers the loop does not have): the optical depth is the interpolant alone and the tile's chi^2 a
+    // quadratic form in its series on moments of the data (ff_moment_chi) -- no pixel is loaded, no Horner's rule, no
+    // exponential per pixel.  The guard (vamp::ff_moments_ok) admits a tile only where the form's cancellation is harmless:
+    // first on what the data alone say (amax = 0), then with the largest absorption at the nodes.  A tile it turns away is
+    // not marked and is swept pixel by pixel below like any other.  Every decision is wave-uniform.  The mark of a tile
+    // that is done: all sixteen bits of its field in BOTH masks -- the classification never lists a line as far and wide --
+    // so that the loop below carries no state it did not carry before.
+#if VAMP_TILE_MOMENTS && !defined(VAMP_SKIP_FFNODES)
+    {
+        unsigned long long fm = farmasks, wm = widemasks;
+#pragma unroll 1
+        for (int j = 0; j < FF_BATCH; ++j, fm >>= KMAX, wm >>= KMAX) {
+            const int base = batch + j * stride;
+            if (base >= base1) break;
+            const unsigned farmask = (unsigned)fm & 0xffffu, widemask = WIDE ? (unsigned)wm & 0xffffu : 0u;
+            if ((~(farmask | widemask) & ((1u << K) - 1u)) != 0u) continue;
+            const double* mt = mom + (base >> 8) * vamp::FFM_TILE;
+            const double root_c0 = mt[vamp::FFM_RC], root_q0 = mt[vamp::FFM_RQ];
+            if (!vamp::ff_moments_try(root_c0, root_q0)) continue;
+            const double2 tg = geo[base >> 8];
+            const double mid = tg.x, half = fabs(tg.y);
+            const int nfar = __builtin_popcount(farmask), nwide = __builtin_popcount(widemask);
+            const int ln = lane_here();       // (this loop keeps nothing derived from the lane index between its tiles)
+            double fs_wide = 0.0;
+            if constexpr (WIDE) {
+                if (nwide > 0) fs_wide = ff_wide_nodes<typename PK::Lds>(L, Sx.widelist[j], dct, tab, ln, nwide, mid, half);
+            }
+            const double fs = ff_node_sums<typename PK::Lds, GUARD>(L, Sx.farlist[j], dct, ln, nfar, mid, half, fs_wide);
+            int eoff = FF_EXP;
+            asm volatile("" : "+s"(eoff));          // (as below: the constants are read here, not kept in registers)
+            const double a = -vamp::expm1_taylor_tab(-fs, dct + eoff);
+            const double amax = row16_max(fabs(a));      // (every row of 16 lanes holds the 16 nodes)
+            if (!__builtin_amdgcn_readfirstlane((int)vamp::ff_moments_ok(root_c0, root_q0, amax))) continue;
+            ff_moment_chi(Sx, dct, mt, ln, a, chi);
+            const unsigned long long field = 0xffffull << (KMAX * j);
+            farmasks |= field;
+            widemasks |= field;
+        }
+    }
+#endif
 #pragma unroll 1
     for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX, zonemasks >>= KMAX) {
         const int base = batch + j * stride;
@@ -1077,6 +1187,7 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             tau[t] = 0.0;
         }
 #endif
+        if ((unsigned)farmasks & (unsigned)widemasks & 0xffffu) continue;      // done from its moments
         // tile geometry (wave-uniform): the table's half carries the grid's orientation in its sign
         const double2 tg = geo[base >> 8];
         const double mid = tg.x, half = fabs(tg.y);
@@ -1438,6 +1549,7 @@ struct PixPtrs {
     // quarters, indexed like x (fp64 contexts: u, fp32 contexts: uf), and (mid, +-half) of the tile that starts at
     // global pixel g in geo[g >> 8]
     const double* u; const float* uf; const double2* geo;
+    const double* mom;      // fp64 contexts: the data moments of the tile in geo's slot s at mom + s FFM_TILE (ff_moments.hpp), or null
 };
 
 // The far-field tables of a context, built once per vamp_set_regions: what the tile loop used to recompute for every
@@ -1449,7 +1561,8 @@ struct PixPtrs {
 template <bool F32>
 __global__ __launch_bounds__(64 * TPIX) void k_tile_tables(const RegionDev* __restrict__ regions, const double* __restrict__ x,
                                                            const float* __restrict__ xf, double* __restrict__ u, float* __restrict__ uf,
-                                                           double2* __restrict__ geo) {
+                                                           double2* __restrict__ geo, const double* __restrict__ f = nullptr,
+                                                           const double* __restrict__ wt = nullptr, double* __restrict__ mom = nullptr) {
     const RegionDev& R = regions[blockIdx.y];
     const int base = (int)blockIdx.x * (64 * TPIX), i = base + (int)threadIdx.x;
     if (i >= R.P) return;
@@ -1464,15 +1577,49 @@ __global__ __launch_bounds__(64 * TPIX) void k_tile_tables(const RegionDev* __re
     const double mid = 0.5 * (x_lo + x_hi), half = 0.5 * fabs(x_hi - x_lo);
     const bool up = x_hi > x_lo;
     const int t = (int)threadIdx.x >> 6, q = up ? t : TPIX - 1 - t;
+    double ug = 0.0;
     if constexpr (F32) {
         const float hf = (float)half, mf = (float)mid;
         const float scale = 4.0f * __builtin_amdgcn_rcpf(hf);
         uf[g] = (xf[g] - fmaf(hf, 0.5f * q - 0.75f, mf)) * scale;
     } else {
         const double scale = 4.0 * vamp::rcp_nr(half);     // (a last-bit error in the scale moves u by 1e-16)
-        u[g] = (x[g] - fma(half, 0.5 * q - 0.75, mid)) * scale;
+        ug = (x[g] - fma(half, 0.5 * q - 0.75, mid)) * scale;
+        u[g] = ug;
     }
     if (threadIdx.x == 0) geo[g0 >> 8] = make_double2(mid, up ? half : -half);
+#if VAMP_TILE_MOMENTS
+    // data moments of the tile (ff_moments.hpp): wavefront t holds quarter q, one pixel per lane; every sum in the one
+    // order of wave_sum's tree, the powers of u by repeated multiplication
+    if constexpr (!F32) {
+        __shared__ double part[TPIX][2];
+        double* mt = mom + (g0 >> 8) * vamp::FFM_TILE;
+        const int lane = (int)threadIdx.x & 63;
+        const double w2 = wt[g] * wt[g], d = f[g] - 1.0, w2d = w2 * d;
+        double pw = 1.0;
+        for (int n = 0; n < vamp::FFM_NQ; ++n) {
+            const double sq = wave_sum<64>(w2 * pw);
+            if (lane == 0) mt[q * vamp::FFM_QROW + n] = sq;
+            if (n == 0 && lane == 0) part[q][0] = sq;
+            if (n < vamp::FFM_NS) {
+                const double ss = wave_sum<64>(w2d * pw);
+                if (lane == 0) mt[vamp::FFM_S + q * vamp::FFM_NS + n] = ss;
+            }
+            pw *= ug;
+        }
+        const double c0 = wave_sum<64>(w2d * d);
+        if (lane == 0) part[q][1] = c0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double q0 = (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]);
+            const double C0 = (part[0][1] + part[1][1]) + (part[2][1] + part[3][1]);
+            mt[vamp::FFM_C0] = C0;
+            mt[vamp::FFM_RC] = sqrt(C0);
+            mt[vamp::FFM_RQ] = sqrt(q0);
+            mt[3 * vamp::FFM_QROW + vamp::FFM_NQ] = 0.0;
+        }
+    }
+#endif
 }
 
 // Sum over the walker's pixels of ((f - m) w)^2, on every lane.  One walker per wavefront (LPW = 64):
@@ -1513,6 +1660,7 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
             // a tile starts at a multiple of 256 pixels of its region, so tile `base` is slot (pix_off >> 8) + (base >> 8)
             const double* ut = px.u + R.pix_off;
             const double2* geo = px.geo + (R.pix_off >> 8);
+            const double* mom = VAMP_TILE_MOMENTS ? px.mom + (R.pix_off >> 8) * vamp::FFM_TILE : nullptr;
             // what stage_lines left in the parameter block: the mask of the lines far wider than a tile (none on a
             // converged ensemble) and, above it, the walker's guard bits (ff_guard_bits)
             const int flags = __builtin_amdgcn_readfirstlane((int)(__double_as_longlong(L.theta[4 * PK::KCAP + 2]) & 0x3ffff));
@@ -1520,15 +1668,15 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
             if constexpr (VAMP_WIDE_NODES && TAB) {
                 const unsigned long long wide_all = (unsigned long long)(flags & 0xffff);
                 if (VAMP_MID_NODES || wide_all) {
-                    if (guard) sweep_range_ff<MODE, PK, TAB, true, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all);
-                    else sweep_range_ff<MODE, PK, TAB, true, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all);
+                    if (guard) sweep_range_ff<MODE, PK, TAB, true, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
+                    else sweep_range_ff<MODE, PK, TAB, true, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
                 } else {
-                    if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
-                    else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
+                    if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                    else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
                 }
             } else {
-                if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
-                else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab);
+                if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
             }
         } else if (TPIX > 1) sweep_range<MODE, PK, TPIX, TAB>(R, L, x, f, wt, lane, base0, full, stride, chi, tab);
         if constexpr (PK::TAIL || TPIX == 1)
@@ -2610,9 +2758,10 @@ struct vamp_ctx : vamp::AbiState {
     DevBuf<double> u_d;
     DevBuf<float> uf_d;
     DevBuf<double2> geo_d;
+    DevBuf<double> mom_d;            // (fp64 contexts built with VAMP_TILE_MOMENTS)
 
     PixPtrs pix() const {
-        return PixPtrs{x_d.get(), f_d.get(), wt_d.get(), xf_d.get(), ff_d.get(), wtf_d.get(), u_d.get(), uf_d.get(), geo_d.get()};
+        return PixPtrs{x_d.get(), f_d.get(), wt_d.get(), xf_d.get(), ff_d.get(), wtf_d.get(), u_d.get(), uf_d.get(), geo_d.get(), mom_d.get()};
     }
 };
 
@@ -2623,7 +2772,7 @@ void reset_regions(vamp_ctx* c) {
     c->regions_d.reset();
     c->x_d.reset(); c->f_d.reset(); c->wt_d.reset();
     c->xf_d.reset(); c->ff_d.reset(); c->wtf_d.reset();
-    c->u_d.reset(); c->uf_d.reset(); c->geo_d.reset();
+    c->u_d.reset(); c->uf_d.reset(); c->geo_d.reset(); c->mom_d.reset();
     c->classes.clear();
     c->classes_small.clear();
     c->n_regions = 0;
@@ -3347,9 +3496,10 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
         if (c->f32) HIP_TRY(c->uf_d.ensure(N));
         else HIP_TRY(c->u_d.ensure(N));
         HIP_TRY(c->geo_d.ensure(N / (64 * TPIX) + 1));
+        if (VAMP_TILE_MOMENTS && !c->f32) HIP_TRY(c->mom_d.ensure((N / (64 * TPIX) + 1) * vamp::FFM_TILE));
         VAMP_FOR_F32(c->f32, hipLaunchKernelGGL((k_tile_tables<F32>), dim3((unsigned)max_tiles, (unsigned)n_regions), dim3(64 * TPIX), 0,
                                                 c->stream, c->regions_d.get(), c->x_d.get(), c->xf_d.get(), c->u_d.get(),
-                                                c->uf_d.get(), c->geo_d.get()));
+                                                c->uf_d.get(), c->geo_d.get(), c->f_d.get(), c->wt_d.get(), c->mom_d.get()));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(c->stream));      // (the stream may be exchanged before the first sweep)
     }

@@ -131,6 +131,20 @@ VAMP_DEV double exp_taylor_tab(double a, const double* c) {
     p = fma(p, r, 1.0);
     return ldexp(p, (int)n);
 }
+// e^a - 1 on the same constants (the full degree-13 kernel): e^r - 1 = r P(r) keeps its relative accuracy where e^a
+// rounds to 1, and 2^n (r P) + (2^n - 1) is exact in its second term.  For the absorption 1 - e^{-tau} of a shallow tile.
+VAMP_DEV double expm1_taylor_tab(double a, const double* c) {
+    a = (a < -800.0) ? -800.0 : a;
+    const double n = rint(a * c[0]);
+    double r = fma(-n, c[1], a);
+    r = fma(-n, c[2], r);
+    double p = c[3];
+#pragma unroll
+    for (int k = 4; k <= 14; ++k) p = fma(p, r, c[k]);
+    p = fma(p, r, 1.0);
+    const double s = ldexp(1.0, (int)n);
+    return fma(s, p * r, s - 1.0);
+}
 VAMP_DEV double exp_neg_sq_tab(double x, const double* c) {
     double s = x * x;
     double e = fma(x, x, -s);
