@@ -6,7 +6,9 @@
   python tools/variants.py runc3 [steps] [extra args...]         (the same on tools/bench_c3.py, config 3)
 
 Switches of the far-field tile loop that have a build of their own (see the #ifndef block at the top of vamp_hip.hip):
-  mom0=-DVAMP_TILE_MOMENTS=0     every tile pixel by pixel (default 1: tiles without a near line from the data moments)
+  mom1=-DVAMP_TILE_MOMENTS=1     tiles without a near line from the data moments of the tile's four series (default 2: from the
+                                 node record, a quadratic form in the 16 node values)
+  mom0=-DVAMP_TILE_MOMENTS=0     every tile pixel by pixel
 """
 import json
 import os

@@ -20,6 +20,23 @@ constexpr int FFM_C0 = 0 * FFM_QROW + FFM_NQ;       // spare slot of quarter 0: 
 constexpr int FFM_RC = 1 * FFM_QROW + FFM_NQ;       // ... of quarter 1: sqrt(C0)
 constexpr int FFM_RQ = 2 * FFM_QROW + FFM_NQ;       // ... of quarter 2: sqrt(Q_0[0] + Q_1[0] + Q_2[0] + Q_3[0])
 
+// The node record (VAMP_TILE_MOMENTS == 2, the default): the same chi^2 written on the values a_n of the absorption at the
+// tile's 16 Chebyshev nodes instead of the series they are transformed into.  The tile's interpolant is
+// a(x) = sum_n l_n(t(x)) a_n with l_n the Lagrange basis of the nodes t_n on t = (x - mid) / half, so
+//     sum w^2 ((f - 1) + a)^2 = C0 + sum_n a_n (2 S'_n + sum_m Q'_nm a_m),
+//     S'_n = sum w^2 (f - 1) l_n,   Q'_nm = sum w^2 l_n l_m   (symmetric; sum_nm Q'_nm = sum w^2 since sum_n l_n = 1).
+// The node abscissae are mid + half t_n whatever the grid's orientation, so the record needs no quarters.
+// Layout of one tile, in doubles: Q'[16][16] row by row, S'[16], then C0, sqrt(C0), sqrt(sum w^2); padded to whole
+// 64-byte lines (lane 16 g + n reads columns 4 g .. 4 g + 3 of row n: 32 aligned bytes).
+constexpr int FFN_NODES = 16;
+constexpr int FFN_Q = 0;
+constexpr int FFN_S = FFN_NODES * FFN_NODES;        // offset of S'
+constexpr int FFN_C0 = FFN_S + FFN_NODES;           // C0
+constexpr int FFN_RC = FFN_C0 + 1;                  // sqrt(C0)
+constexpr int FFN_RQ = FFN_C0 + 2;                  // sqrt(sum w^2)
+constexpr int FFN_TILE = 280;                       // doubles per tile
+static_assert(FFN_TILE >= FFN_RQ + 1 && FFN_TILE % 8 == 0, "the record fits, and a tile starts on a 64-byte line");
+
 // The moment form is a sum with cancellation: its terms are bounded by M = (sqrt(C0) + amax sqrt(sum_q Q_q[0]))^2 with amax
 // the largest |a| at the tile's nodes (Cauchy-Schwarz on sum w^2 (|f - 1| + |a|)^2), and its rounding error is about
 // FFM_ULPS 2^-53 M.  A tile takes the moment form only if that is at most FFM_BOUND = 2^-40 x 256: 1e-12 of the chi^2 of a

@@ -113,8 +113,8 @@
 #define VAMP_F32_LEAN_STAGE 1
 #endif
 #ifndef VAMP_TILE_MOMENTS
-#define VAMP_TILE_MOMENTS 1    // fp64 far-field loop: chi^2 of a tile without a near line from the context's data moments (ff_moments.hpp);
-#endif                         // 0: every tile pixel by pixel
+#define VAMP_TILE_MOMENTS 2    // fp64 far-field loop: chi^2 of a tile without a near line from the context's data moments (ff_moments.hpp):
+#endif                         // 2: a quadratic form in the 16 node values; 1: in the four series of the tile; 0: every tile pixel by pixel
 namespace {
 
 constexpr int KMAX = 16;                       // lines per region of the fast shapes (far field, Taylor tables, packing)
@@ -1036,6 +1036,30 @@ __device__ __forceinline__ void ff_moment_chi(TileScratch& Sx, const double* __r
     chi += lane < FF_ROWS ? term : lane == FF_ROWS ? c0 : 0.0;
     __builtin_amdgcn_wave_barrier();
 }
+// (d') the same chi^2 from the tile's node record (ff_moments.hpp, VAMP_TILE_MOMENTS == 2): a quadratic form in the node
+//     values themselves, C0 + sum_n a_n (2 S'_n + sum_m Q'_nm a_m) -- no transform, no series.  Every row of 16 lanes
+//     holds the 16 values; lane 16 g + n takes row n, columns 4 g .. 4 g + 3 of Q' (32 contiguous bytes) and a quarter of
+//     2 S'_n (S'_n / 2 four times is 2 S'_n exactly); lane 0 adds C0.  The four a_m of a lane's columns come from the
+//     first row's copy in Sx.coef at a row-uniform address.
+__device__ __forceinline__ void ff_moment_chi_nodes(TileScratch& Sx, const double* __restrict__ mt, int lane, double a, double c0, double& chi) {
+    static_assert(FF_NODES == vamp::FFN_NODES, "the record is laid out for the node stage's 16 nodes");
+    if (lane < FF_NODES) Sx.coef[lane] = a;
+    const int n = lane & (FF_NODES - 1), g4 = (lane >> 4) * 4;
+    const double2* Qr = reinterpret_cast<const double2*>(mt + vamp::FFN_Q + n * FF_NODES + g4);
+    const double2 q01 = Qr[0], q23 = Qr[1];
+    const double Sv = mt[vamp::FFN_S + n];
+    __builtin_amdgcn_wave_barrier();
+    const double2* av = reinterpret_cast<const double2*>(Sx.coef + g4);
+    const double2 a01 = av[0], a23 = av[1];
+    const double acc0 = fma(q01.x, a01.x, 0.5 * Sv), acc1 = q01.y * a01.y;
+    const double term = a * (fma(q23.x, a23.x, acc0) + fma(q23.y, a23.y, acc1));
+    chi += lane == 0 ? term + c0 : term;
+    __builtin_amdgcn_wave_barrier();
+}
+// the tile's record in the context's table: its size and the places of what the guard reads
+constexpr int MOM_TILE = VAMP_TILE_MOMENTS == 2 ? vamp::FFN_TILE : vamp::FFM_TILE;
+constexpr int MOM_RC = VAMP_TILE_MOMENTS == 2 ? vamp::FFN_RC : vamp::FFM_RC;
+constexpr int MOM_RQ = VAMP_TILE_MOMENTS == 2 ? vamp::FFN_RQ : vamp::FFM_RQ;
 // ---- lines far wider than the tile -------------------------------------------------------------------------------
 // An ensemble drawn from the priors (widths ~ U(0, fwhm_max): where every find_bic repeat STARTS, vpfits.py:283-297) has
 // nothing far: every line is wider than the region, every (line, tile) pair is near and costs four table look-ups per
@@ -1125,7 +1149,8 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
     ff_classify_batch<WIDE, false, TAB>(L, Sx, geo, K, lane, batch, base1, stride, (unsigned)wide_all, farmasks, widemasks, zonemasks);
     // Tiles without a near line, in a loop of their own ahead of the others' (compiled into the one loop the branch costs
     // every tile registers the loop does not have): the optical depth is the interpolant alone and the tile's chi^2 a
-    // quadratic form in its series on moments of the data (ff_moment_chi) -- no pixel is loaded, no Horner's rule, no
+    // quadratic form in its 16 node values on the tile's node record (ff_moment_chi_nodes; VAMP_TILE_MOMENTS == 1: in its
+    // series on moments of the data, ff_moment_chi) -- no pixel is loaded, no transform, no Horner's rule, no
     // exponential per pixel.  The guard (vamp::ff_moments_ok) admits a tile only where the form's cancellation is harmless:
     // first on what the data alone say (amax = 0), then with the largest absorption at the nodes.  A tile it turns away is
     // not marked and is swept pixel by pixel below like any other.  Every decision is wave-uniform.  The mark of a tile
@@ -1140,8 +1165,8 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             if (base >= base1) break;
             const unsigned farmask = (unsigned)fm & 0xffffu, widemask = WIDE ? (unsigned)wm & 0xffffu : 0u;
             if ((~(farmask | widemask) & ((1u << K) - 1u)) != 0u) continue;
-            const double* mt = mom + (base >> 8) * vamp::FFM_TILE;
-            const double root_c0 = mt[vamp::FFM_RC], root_q0 = mt[vamp::FFM_RQ];
+            const double* mt = mom + (base >> 8) * MOM_TILE;
+            const double root_c0 = mt[MOM_RC], root_q0 = mt[MOM_RQ];
             if (!vamp::ff_moments_try(root_c0, root_q0)) continue;
             const double2 tg = geo[base >> 8];
             const double mid = tg.x, half = fabs(tg.y);
@@ -1157,7 +1182,11 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             const double a = -vamp::expm1_taylor_tab(-fs, dct + eoff);
             const double amax = row16_max(fabs(a));      // (every row of 16 lanes holds the 16 nodes)
             if (!__builtin_amdgcn_readfirstlane((int)vamp::ff_moments_ok(root_c0, root_q0, amax))) continue;
+#if VAMP_TILE_MOMENTS == 2
+            ff_moment_chi_nodes(Sx, mt, ln, a, mt[vamp::FFN_C0], chi);
+#else
             ff_moment_chi(Sx, dct, mt, ln, a, chi);
+#endif
             const unsigned long long field = 0xffffull << (KMAX * j);
             farmasks |= field;
             widemasks |= field;
@@ -1549,7 +1578,7 @@ struct PixPtrs {
     // quarters, indexed like x (fp64 contexts: u, fp32 contexts: uf), and (mid, +-half) of the tile that starts at
     // global pixel g in geo[g >> 8]
     const double* u; const float* uf; const double2* geo;
-    const double* mom;      // fp64 contexts: the data moments of the tile in geo's slot s at mom + s FFM_TILE (ff_moments.hpp), or null
+    const double* mom;      // fp64 contexts: the record of the tile in geo's slot s at mom + s MOM_TILE (ff_moments.hpp), or null
 };
 
 // The far-field tables of a context, built once per vamp_set_regions: what the tile loop used to recompute for every
@@ -1588,7 +1617,64 @@ __global__ __launch_bounds__(64 * TPIX) void k_tile_tables(const RegionDev* __re
         u[g] = ug;
     }
     if (threadIdx.x == 0) geo[g0 >> 8] = make_double2(mid, up ? half : -half);
-#if VAMP_TILE_MOMENTS
+#if VAMP_TILE_MOMENTS == 2
+    // node record of the tile (ff_moments.hpp).  The Lagrange basis of the 16 nodes t_n at the pixel's t = (x - mid) / half
+    // in its barycentric form, l_n = (w_n / (t - t_n)) / sum_m w_m / (t - t_m) with w_n = (-1)^n sqrt((1 - t_n)(1 + t_n));
+    // a pixel AT a node has l = 1 there and 0 elsewhere.  Then thread (n, m) sums w^2 (l_n l_m) over the tile's 256 pixels
+    // (eight chains over the pixels i = k mod 8, added as a tree: one fixed order, and Q' symmetric to the bit), threads
+    // 0 .. 15 sum S' as well.  C0 and sum w^2 -- what is left of chi^2 where the absorption is shallow -- in wave_sum's tree.
+    if constexpr (!F32) {
+        constexpr int NN = vamp::FFN_NODES, NPIX = 64 * TPIX;
+        __shared__ double ell[NN][NPIX];
+        __shared__ double w2s[NPIX], w2ds[NPIX], part[TPIX][2];
+        const int p = (int)threadIdx.x;
+        const double tp = (x[g] - mid) / half;
+        double c[NN], den = 0.0;
+        int hit = -1;
+#pragma unroll
+        for (int n = 0; n < NN; ++n) {
+            const double tn = FF_M[FF_MAT + n], wn = sqrt((1.0 - tn) * (1.0 + tn)), diff = tp - tn;
+            if (diff == 0.0) hit = n;
+            c[n] = ((n & 1) ? -wn : wn) / diff;
+            den += c[n];
+        }
+#pragma unroll
+        for (int n = 0; n < NN; ++n) ell[n][p] = hit < 0 ? c[n] / den : (n == hit ? 1.0 : 0.0);
+        const double w2 = wt[g] * wt[g], d = f[g] - 1.0, w2d = w2 * d;
+        w2s[p] = w2;
+        w2ds[p] = w2d;
+        __syncthreads();
+        double* mt = mom + (g0 >> 8) * vamp::FFN_TILE;
+        const int n = p >> 4, m = p & (NN - 1);
+        double qa[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, sa[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int i = 0; i < NPIX; i += 8) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) qa[k] = fma(w2s[i + k], ell[n][i + k] * ell[m][i + k], qa[k]);
+        }
+        mt[vamp::FFN_Q + p] = ((qa[0] + qa[1]) + (qa[2] + qa[3])) + ((qa[4] + qa[5]) + (qa[6] + qa[7]));
+        if (p < NN) {
+            for (int i = 0; i < NPIX; i += 8) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) sa[k] = fma(w2ds[i + k], ell[p][i + k], sa[k]);
+            }
+            mt[vamp::FFN_S + p] = ((sa[0] + sa[1]) + (sa[2] + sa[3])) + ((sa[4] + sa[5]) + (sa[6] + sa[7]));
+        }
+        const double cw = wave_sum<64>(w2d * d), qw = wave_sum<64>(w2);
+        if ((p & 63) == 0) {
+            part[p >> 6][0] = qw;
+            part[p >> 6][1] = cw;
+        }
+        __syncthreads();
+        if (p == 0) {
+            const double q0 = (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]);
+            const double C0 = (part[0][1] + part[1][1]) + (part[2][1] + part[3][1]);
+            mt[vamp::FFN_C0] = C0;
+            mt[vamp::FFN_RC] = sqrt(C0);
+            mt[vamp::FFN_RQ] = sqrt(q0);
+        }
+        if (p > vamp::FFN_RQ - vamp::FFN_S && p < vamp::FFN_TILE - vamp::FFN_S) mt[vamp::FFN_S + p] = 0.0;      // the padding
+    }
+#elif VAMP_TILE_MOMENTS
     // data moments of the tile (ff_moments.hpp): wavefront t holds quarter q, one pixel per lane; every sum in the one
     // order of wave_sum's tree, the powers of u by repeated multiplication
     if constexpr (!F32) {
@@ -1660,7 +1746,7 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
             // a tile starts at a multiple of 256 pixels of its region, so tile `base` is slot (pix_off >> 8) + (base >> 8)
             const double* ut = px.u + R.pix_off;
             const double2* geo = px.geo + (R.pix_off >> 8);
-            const double* mom = VAMP_TILE_MOMENTS ? px.mom + (R.pix_off >> 8) * vamp::FFM_TILE : nullptr;
+            const double* mom = VAMP_TILE_MOMENTS ? px.mom + (R.pix_off >> 8) * MOM_TILE : nullptr;
             // what stage_lines left in the parameter block: the mask of the lines far wider than a tile (none on a
             // converged ensemble) and, above it, the walker's guard bits (ff_guard_bits)
             const int flags = __builtin_amdgcn_readfirstlane((int)(__double_as_longlong(L.theta[4 * PK::KCAP + 2]) & 0x3ffff));
@@ -2758,7 +2844,7 @@ struct vamp_ctx : vamp::AbiState {
     DevBuf<double> u_d;
     DevBuf<float> uf_d;
     DevBuf<double2> geo_d;
-    DevBuf<double> mom_d;            // (fp64 contexts built with VAMP_TILE_MOMENTS)
+    DevBuf<double> mom_d;            // (fp64 contexts built with VAMP_TILE_MOMENTS: MOM_TILE doubles per slot of geo_d)
 
     PixPtrs pix() const {
         return PixPtrs{x_d.get(), f_d.get(), wt_d.get(), xf_d.get(), ff_d.get(), wtf_d.get(), u_d.get(), uf_d.get(), geo_d.get(), mom_d.get()};
@@ -3371,6 +3457,20 @@ long long vampdbg_tile_tables(vamp_ctx* c, double* u_out, float* uf_out, double*
     return slots;
 }
 
+// Test hook, not part of the header: the tiles' records behind the moment form (k_tile_tables, ff_moments.hpp), slot by
+// slot like geo: out [slots x doubles per tile].  With out == nullptr nothing is copied.  Returns the doubles per tile
+// (FFN_TILE or FFM_TILE, as the library was built), 0 when the context holds no record, or an error code.
+long long vampdbg_tile_moments(vamp_ctx* c, double* out) {
+    if (!c) return fail(VAMP_ERR_ARG, "vampdbg_tile_moments: bad argument");
+    if (c->regions_h.empty()) return fail(VAMP_ERR_STATE, "vampdbg_tile_moments: call vamp_set_regions first");
+    if (!VAMP_TILE_MOMENTS || c->f32 || !c->geo_d || !c->mom_d) return 0;
+    const long long N = c->regions_h.back().pix_off + c->regions_h.back().P;
+    const long long slots = N / (64 * TPIX) + 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (out) HIP_TRY(hipMemcpy(out, c->mom_d.get(), slots * MOM_TILE * sizeof(double), hipMemcpyDeviceToHost));
+    return MOM_TILE;
+}
+
 int vamp_version(void) { return VAMP_ABI_VERSION; }
 
 const char* vamp_last_error(void) { return vamp::last_error().c_str(); }
@@ -3496,7 +3596,10 @@ int vamp_set_regions(vamp_ctx* c, int n_regions, const int64_t* pix_off, const d
         if (c->f32) HIP_TRY(c->uf_d.ensure(N));
         else HIP_TRY(c->u_d.ensure(N));
         HIP_TRY(c->geo_d.ensure(N / (64 * TPIX) + 1));
-        if (VAMP_TILE_MOMENTS && !c->f32) HIP_TRY(c->mom_d.ensure((N / (64 * TPIX) + 1) * vamp::FFM_TILE));
+        if (VAMP_TILE_MOMENTS && !c->f32) {       // (cleared: a slot without a full tile holds no record, vampdbg_tile_moments shows it)
+            HIP_TRY(c->mom_d.ensure((N / (64 * TPIX) + 1) * MOM_TILE));
+            HIP_TRY(hipMemsetAsync(c->mom_d.get(), 0, (N / (64 * TPIX) + 1) * MOM_TILE * sizeof(double), c->stream));
+        }
         VAMP_FOR_F32(c->f32, hipLaunchKernelGGL((k_tile_tables<F32>), dim3((unsigned)max_tiles, (unsigned)n_regions), dim3(64 * TPIX), 0,
                                                 c->stream, c->regions_d.get(), c->x_d.get(), c->xf_d.get(), c->u_d.get(),
                                                 c->uf_d.get(), c->geo_d.get(), c->f_d.get(), c->wt_d.get(), c->mom_d.get()));
