@@ -9,6 +9,8 @@ Switches of the far-field tile loop that have a build of their own (see the #ifn
   mom1=-DVAMP_TILE_MOMENTS=1     tiles without a near line from the data moments of the tile's four series (default 2: from the
                                  node record, a quadratic form in the 16 node values)
   mom0=-DVAMP_TILE_MOMENTS=0     every tile pixel by pixel
+  np0=-DVAMP_NODE_PASS=0         the node stage tile by tile from the tiles' far and wide lists (default 1: line by line over a
+                                 full batch of four tiles, lane = (tile, node))
 """
 import json
 import os

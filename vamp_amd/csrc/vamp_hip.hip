@@ -115,6 +115,9 @@
 #ifndef VAMP_TILE_MOMENTS
 #define VAMP_TILE_MOMENTS 2    // fp64 far-field loop: chi^2 of a tile without a near line from the context's data moments (ff_moments.hpp):
 #endif                         // 2: a quadratic form in the 16 node values; 1: in the four series of the tile; 0: every tile pixel by pixel
+#ifndef VAMP_NODE_PASS
+#define VAMP_NODE_PASS 1       // fp64 far-field loop: the node values of a full batch of four tiles line by line, lane = (tile, node)
+#endif                         // (ff_node_pass, sweep_range_ff_np); 0: tile by tile from the tiles' lists (ff_node_sums)
 namespace {
 
 constexpr int KMAX = 16;                       // lines per region of the fast shapes (far field, Taylor tables, packing)
@@ -1316,6 +1319,312 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
     }
 }
 
+// ---- the node stage of a full batch, line by line (VAMP_NODE_PASS) ----------------------------------------------------
+// (The timing-only builds of the phase split, the series form of the moments and the prefetching loop keep sweep_range_ff.)
+#if VAMP_NODE_PASS && VAMP_TILE_MOMENTS != 1 && !VAMP_X_PREFETCH && !defined(VAMP_SKIP_NEAR) && !defined(VAMP_SKIP_FFNODES) && \
+    !defined(VAMP_SKIP_CLENSHAW) && !defined(VAMP_SKIP_EXP)
+#define VAMP_NODE_PASS_ON 1
+#else
+#define VAMP_NODE_PASS_ON 0
+#endif
+#if VAMP_NODE_PASS_ON
+// ff_classify_batch judges 16 lines against four tiles with lane = 16 j + k.  The node stage of the same four tiles takes
+// the transposed mapping, lane = 16 j + node, and a loop over the lines that are far for at least one of them: a line's
+// record is read at a wave-uniform address (no lists, no list positions, no clamps), every lane accumulates its own node
+// (no sum across lanes), and the fraction's depth is chosen per pair of lines from the classification's own edge bound.
+__device__ __forceinline__ unsigned ff_fold16(unsigned long long m) {       // OR of the four tiles' 16-bit fields
+    const unsigned h = (unsigned)m | (unsigned)(m >> 32);
+    return (h | (h >> 16)) & 0xffffu;
+}
+// the per-batch sets of lines, nested: n6 <= n4 <= n3 <= far (bit k: line k is far for some tile of the batch and the
+// deepest fraction any of those tiles needs has at least that many levels), and the lines wide for some tile
+struct NodeSets { unsigned far, n6, n4, n3, wide; };
+// The classification of a FULL batch for the fp64 loop: ff_classify_batch's masks without its lists, plus the depth class
+// of every far pair from r2e = (dist s)^2 + y^2.  Every node of the tile lies inside it, at least `dist` from the line's
+// centre, so r2e is a lower bound of r2 at every node, and a deeper fraction is valid wherever a shallower one is.
+// Leaves (mid, half) of the lane's tile j = lane >> 4 with the caller: the node pass wants them on the same lanes.
+template <bool WIDE, bool ZONE, class LDS>
+__device__ __forceinline__ void ff_classify_batch_np(const LDS& L, const double2* __restrict__ geo, int K, int lane_, int base, int stride,
+                                                     unsigned wide_all, unsigned long long& farmasks, unsigned long long& widemasks,
+                                                     unsigned long long& zonemasks, NodeSets& sets, double& mid, double& half) {
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    const int j = lane >> 4, k = lane & (KMAX - 1);
+    const double2 g = geo[(base + j * stride) >> 8];
+    mid = g.x, half = fabs(g.y);
+    const LineRec& me = *reinterpret_cast<const LineRec*>(reinterpret_cast<const char*>(L.line) +
+                                                          __umul24((unsigned)(k < K ? k : 0), (unsigned)sizeof(LineRec)));
+    const double my_c = me.c, my_s = me.s, my_y = me.y, my_w8 = me.w8, my_wmid = me.wmid;
+    const double dist = fabs(mid - my_c) - half;
+    const bool my_beyond = (k < K) & (dist >= FF_DIST * half);
+    const bool my_far = my_beyond & (dist >= my_w8);
+    const double Xe = dist * my_s, r2e = fma(Xe, Xe, my_y * my_y);
+    farmasks = __ballot(my_far);
+    sets.far = ff_fold16(farmasks);
+    sets.n6 = ff_fold16(__ballot(my_far & (r2e < VAMP_FF_R2_M4)));
+    sets.n4 = ff_fold16(__ballot(my_far & (r2e < VAMP_FF_R2_M3)));
+    sets.n3 = ff_fold16(__ballot(my_far & (r2e < VAMP_FF_R2_M2)));
+    widemasks = 0ull;
+    if constexpr (WIDE) {       // (never far AND wide for one tile: the mark of a tile done from its moments, as in ff_classify_batch)
+        const bool my_wide = ((((wide_all >> k) & 1u) != 0u) | (VAMP_MID_NODES && (my_beyond & (dist >= my_wmid)))) & !my_far;
+        widemasks = __ballot(my_wide);
+    }
+    sets.wide = ff_fold16(widemasks);
+    zonemasks = 0ull;
+    if constexpr (ZONE) zonemasks = __ballot(vamp::ff_tile_in_zone(my_c, my_s, my_y, mid, half));
+}
+// The node pass: lane 16 j + n ends with the node sum of (tile j, node n) -- far lines through the fractions, two lines per
+// iteration sharing a reciprocal (ff_frac2), deepest class first, M the class of the deeper of the two; then (WIDE) the
+// lines wide or "mid" for some tile through their Taylor tables, ff_wide_nodes' arithmetic.  A lane for whose tile a line
+// is NOT far takes X = FF_X_IDLE in its place: the parent never evaluated a fraction inside |z| < 8, and the partner's
+// value shares the reciprocal.  A walker with a guard bit (GUARD) evaluates its pairs through ff_eval2<true>, which
+// clamps, patches and picks the depth from the arguments themselves (the idle argument asks for the shallowest).
+constexpr double FF_X_IDLE = 64.0;          // |z|^2 >= 4096: every fraction's range, and below X_FAR
+static_assert(FF_X_IDLE * FF_X_IDLE >= VAMP_FF_R2_M2 && FF_X_IDLE < vamp::X_FAR, "the idle argument neither deepens a pair nor needs a guard");
+template <bool WIDE, bool GUARD, class LDS>
+__device__ __forceinline__ double ff_node_pass(const LDS& L, const double* __restrict__ dct, const double* tab, int lane_, double mid, double half,
+                                               unsigned long long farmasks, unsigned long long widemasks, NodeSets sets) {
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    const double xnode = fma(half, dct[FF_MAT + (lane & (FF_NODES - 1))], mid);
+    const unsigned far16 = ff_tile_field(farmasks, lane);
+    double fs = 0.0;
+    unsigned rest = sets.far, n6 = sets.n6, n4 = sets.n4, n3 = sets.n3;
+    while (rest) {
+        const int depth = n6 ? 6 : n4 ? 4 : n3 ? 3 : 2;
+        int kk[2];
+        bool live[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {               // the next line of the deepest class that has one; an odd last line pairs
+            live[t] = rest != 0u;                   // with a copy of itself that no lane adds
+            if (live[t]) {
+                kk[t] = __builtin_ctz(n6 ? n6 : n4 ? n4 : n3 ? n3 : rest);
+                const unsigned keep = ~(1u << kk[t]);
+                rest &= keep, n6 &= keep, n4 &= keep, n3 &= keep;
+            } else {
+                kk[t] = kk[0];
+            }
+        }
+        double X[2], y[2], amp[2], H[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const LineRec& ln = L.line[kk[t]];
+            const bool mine = live[t] & (((far16 >> kk[t]) & 1u) != 0u);
+            X[t] = mine ? fabs(xnode - ln.c) * ln.s : FF_X_IDLE;
+            y[t] = ln.y;
+            amp[t] = mine ? ln.amp : 0.0;
+        }
+        if constexpr (GUARD) {
+            ff_eval2<true>(X, y, H, dct + FF_EXP);
+        } else {
+            const double r2[2] = {fma(X[0], X[0], y[0] * y[0]), fma(X[1], X[1], y[1] * y[1])};
+            if (depth == 6) ff_frac2<6>(X, y, r2, H);
+            else if (depth == 4) ff_frac2<4>(X, y, r2, H);
+            else if (depth == 3) ff_frac2<3>(X, y, r2, H);
+            else ff_frac2<2>(X, y, r2, H);
+        }
+        fs = fma(amp[0], H[0], fs);
+        fs = fma(amp[1], H[1], fs);
+    }
+    if constexpr (WIDE) {
+        const unsigned wide16 = ff_tile_field(widemasks, lane);
+        for (unsigned w = sets.wide; w; w &= w - 1u) {
+            const int k = __builtin_ctz(w);
+            if ((wide16 >> k) & 1u) {
+                const LineRec& ln = L.line[k];
+                const double X = fabs(xnode - ln.c) * ln.s, r2 = fma(X, X, ln.y * ln.y);
+                double H;
+                if (r2 < vamp::R2_CORE) {
+                    H = table_eval(tab + k * vamp::TAB_LINE, X);
+                } else {
+                    H = vamp::voigt_jfrac<6>(X, ln.y, r2);
+                    if (ln.y < vamp::Y_TINY) H += vamp::SQRT_PI * vamp::exp_neg_sq_tab(X, dct + FF_EXP);
+                }
+                fs = fma(ln.amp, H, fs);
+            }
+        }
+    }
+    return fs;
+}
+// ff_series for a value every lane holds for (tile lane >> 4, node lane & 15): row `j` hands over its tile's node values
+template <class real>
+__device__ __forceinline__ void ff_series_row(TileScratch& Sx, const double* __restrict__ dct, int lane, int j, double fs) {
+    if ((lane >> 4) == j) Sx.coef[lane & (FF_NODES - 1)] = fs;
+    __builtin_amdgcn_wave_barrier();
+    const double2* mrow = reinterpret_cast<const double2*>(dct) + (lane < FF_ROWS ? lane : FF_ROWS - 1);
+    const double2* fv = reinterpret_cast<const double2*>(Sx.coef);
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int n2 = 0; n2 < FF_NODES / 2; ++n2) {
+        const double2 m = mrow[n2 * FF_ROWS], f2 = fv[n2];
+        a0 = fma(m.x, f2.x, a0);
+        a1 = fma(m.y, f2.y, a1);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < FF_ROWS) reinterpret_cast<real*>(Sx.coef)[lane] = (real)(a0 + a1);
+    __builtin_amdgcn_wave_barrier();
+}
+// ff_moment_chi_nodes for the absorption every lane holds for (tile lane >> 4, node lane & 15): row `j` hands its 16
+// values over through Sx.coef, and every lane takes its own a_n from there with the a_m of its columns
+__device__ __forceinline__ void ff_moment_chi_nodes_row(TileScratch& Sx, const double* __restrict__ mt, int lane, int j, double a_row, double c0,
+                                                        double& chi) {
+    if ((lane >> 4) == j) Sx.coef[lane & (FF_NODES - 1)] = a_row;
+    const int n = lane & (FF_NODES - 1), g4 = (lane >> 4) * 4;
+    const double2* Qr = reinterpret_cast<const double2*>(mt + vamp::FFN_Q + n * FF_NODES + g4);
+    const double2 q01 = Qr[0], q23 = Qr[1];
+    const double Sv = mt[vamp::FFN_S + n];
+    __builtin_amdgcn_wave_barrier();
+    const double2* av = reinterpret_cast<const double2*>(Sx.coef + g4);
+    const double2 a01 = av[0], a23 = av[1];
+    const double a = Sx.coef[n];
+    const double acc0 = fma(q01.x, a01.x, 0.5 * Sv), acc1 = q01.y * a01.y;
+    const double term = a * (fma(q23.x, a23.x, acc0) + fma(q23.y, a23.y, acc1));
+    chi += lane == 0 ? term + c0 : term;
+    __builtin_amdgcn_wave_barrier();
+}
+// sweep_range_ff with the node stage of every FULL batch done line by line ahead of the batch's tile loops; what is left
+// of the range after its full batches -- all of a range of fewer than FF_BATCH tiles -- goes through sweep_range_ff
+// itself.  Tile order and the per-lane order of the chi additions are sweep_range_ff's.  The near lines, the series,
+// Horner's rule and the exponentials are its arithmetic; the node values differ by the order of their sums and, where a
+// pair is evaluated deeper than before, by the fractions' own differences (1e-13 of a value).
+template <int MODE, class PK, bool TAB, bool WIDE = false, bool GUARD = true>
+__device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const typename PK::Lds& L, TileScratch& Sx, const double* __restrict__ dct,
+                                                  const double* __restrict__ x, const double* __restrict__ f,
+                                                  const double* __restrict__ wt, const double* __restrict__ ut,
+                                                  const double2* __restrict__ geo, int lane, int base0, int base1, int stride,
+                                                  double& chi, const double* tab, unsigned long long wide_all = 0ull,
+                                                  const double* __restrict__ mom = nullptr) {
+    constexpr int T = TPIX;
+    static_assert(PK::LPW == 64 && PK::KCAP <= 16, "far-field tiles: one walker per wavefront, <= 16 lines");
+    const int K = R.K;
+    const int ntile = base0 < base1 ? (base1 - base0 + stride - 1) / stride : 0;
+    // (a wavefront's range is wave-uniform, and so are the batch loop's bounds: said here, because where the range comes
+    //  from the wavefront's index the compiler takes the loop for a divergent one and keeps its counter in a vector register)
+    const int bfull = __builtin_amdgcn_readfirstlane(base0 + (ntile / FF_BATCH) * (FF_BATCH * stride));       // the first tile past the full batches
+    for (int batch = __builtin_amdgcn_readfirstlane(base0); batch < bfull; batch += FF_BATCH * stride) {
+    unsigned long long farmasks, widemasks, zonemasks;
+    double fsn;         // node sum of (tile lane >> 4, node lane & 15): one register pair across the batch's tile loops
+    {
+        NodeSets sets;
+        double mid_j, half_j;
+        ff_classify_batch_np<WIDE, TAB>(L, geo, K, lane, batch, stride, (unsigned)wide_all, farmasks, widemasks, zonemasks, sets, mid_j, half_j);
+        fsn = ff_node_pass<WIDE, GUARD>(L, dct, tab, lane, mid_j, half_j, farmasks, widemasks, sets);
+    }
+#if VAMP_TILE_MOMENTS == 2
+    {   // tiles without a near line (see sweep_range_ff).  The absorption at the nodes and its largest value per tile are
+        // formed once for the batch, when the first tile asks.  ff_moments_try still turns a tile away on the data alone:
+        // the node stage it used to spare is done by now, but on data the form never suits (weights of 1e10) it spares
+        // the batch the exponential, the row maxima and a record's loads
+        unsigned long long fm = farmasks, wm = widemasks;
+        double a_row = 0.0, amax_row = 0.0;
+        bool have_a = false;
+#pragma unroll 1
+        for (int j = 0; j < FF_BATCH; ++j, fm >>= KMAX, wm >>= KMAX) {
+            const unsigned farmask = (unsigned)fm & 0xffffu, widemask = WIDE ? (unsigned)wm & 0xffffu : 0u;
+            if ((~(farmask | widemask) & ((1u << K) - 1u)) != 0u) continue;
+            const double* mt = mom + ((batch + j * stride) >> 8) * MOM_TILE;
+            const double root_c0 = mt[MOM_RC], root_q0 = mt[MOM_RQ];
+            if (!vamp::ff_moments_try(root_c0, root_q0)) continue;
+            if (!have_a) {
+                int eoff = FF_EXP;
+                asm volatile("" : "+s"(eoff));
+                a_row = -vamp::expm1_taylor_tab(-fsn, dct + eoff);
+                amax_row = row16_max(fabs(a_row));
+                have_a = true;
+            }
+            const double amax = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(amax_row), KMAX * j),
+                                                 __builtin_amdgcn_readlane(__double2loint(amax_row), KMAX * j));
+            if (!vamp::ff_moments_ok(root_c0, root_q0, amax)) continue;
+            ff_moment_chi_nodes_row(Sx, mt, lane_here(), j, a_row, mt[vamp::FFN_C0], chi);
+            const unsigned long long field = 0xffffull << (KMAX * j);
+            farmasks |= field;
+            widemasks |= field;
+        }
+    }
+#endif
+#pragma unroll 1
+    for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX, zonemasks >>= KMAX) {
+        const int base = batch + j * stride;
+        double xi[T], tau[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            xi[t] = x[base + 64 * t + lane];
+            tau[t] = 0.0;
+        }
+        if ((unsigned)farmasks & (unsigned)widemasks & 0xffffu) continue;      // done from its moments
+        const bool up = __double2hiint(geo[base >> 8].y) >= 0;
+        const unsigned farmask = (unsigned)farmasks & 0xffffu;
+        const unsigned widemask = WIDE ? (unsigned)widemasks & 0xffffu : 0u;
+        for (unsigned near = ~(farmask | widemask) & ((1u << K) - 1u); near; near &= near - 1u) {
+            const int k = __builtin_ctz(near);
+            const LineRec ln = L.line[k];
+            double X[T], H[T];
+#pragma unroll
+            for (int t = 0; t < T; ++t) X[t] = fabs(xi[t] - ln.c) * ln.s;
+            if (TAB && (((unsigned)zonemasks >> k) & 1u)) {
+#pragma unroll
+                for (int t = 0; t < T; ++t) H[t] = table_eval(tab + k * vamp::TAB_LINE, X[t]);
+            } else {
+                tile_voigt<T, TAB>(ln, dtab_row<PK>(L, k), X, H, TAB ? tab + k * vamp::TAB_LINE : nullptr, dct + FF_EXP);
+            }
+#pragma unroll
+            for (int t = 0; t < T; ++t) tau[t] = fma(ln.amp, H[t], tau[t]);
+        }
+        double fi[T], wi[T];
+        if ((farmask | widemask) != 0u) {
+            // the pixels' places in their quarters: xi has ended with the near lines, u takes its registers; the
+            // transform's LDS reads stand between the request and Horner's rule
+            double u[T];
+#pragma unroll
+            for (int t = 0; t < T; ++t) u[t] = ut[base + 64 * t + lane];
+            ff_series_row<double>(Sx, dct, lane, j, fsn);
+#if VAMP_EARLY_LOADS
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                fi[t] = f[base + 64 * t + lane];
+                wi[t] = wt[base + 64 * t + lane];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+            ff_horner<double, T>(Sx, u, up, tau);
+        } else {
+#if VAMP_EARLY_LOADS
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                fi[t] = f[base + 64 * t + lane];
+                wi[t] = wt[base + 64 * t + lane];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
+        int eoff = FF_EXP;
+        asm volatile("" : "+s"(eoff));          // (as in sweep_range_ff: the exp constants are read per tile, not kept)
+        const double* ec = dct + eoff;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+#if !VAMP_EARLY_LOADS
+            fi[t] = f[base + 64 * t + lane];
+            wi[t] = wt[base + 64 * t + lane];
+#endif
+            const double m = vamp::exp_taylor_tab<VAMP_FLUX_EXP_DROP>(-tau[t], ec);
+            const double r = (fi[t] - m) * wi[t];
+            chi = fma(r, r, chi);
+        }
+    }
+    }
+    if (bfull < base1) sweep_range_ff<MODE, PK, TAB, WIDE, GUARD>(R, L, Sx, dct, x, f, wt, ut, geo, lane, bfull, base1, stride, chi, tab, wide_all, mom);
+}
+#endif
+// the fp64 far-field sweep of a range as the library was built
+template <int MODE, class PK, bool TAB, bool WIDE, bool GUARD, class... Args>
+__device__ __forceinline__ void sweep_range_ff_any(Args&&... args) {
+#if VAMP_NODE_PASS_ON
+    sweep_range_ff_np<MODE, PK, TAB, WIDE, GUARD>(static_cast<Args&&>(args)...);
+#else
+    sweep_range_ff<MODE, PK, TAB, WIDE, GUARD>(static_cast<Args&&>(args)...);
+#endif
+}
+
 #ifndef VAMP_FARFIELD
 #define VAMP_FARFIELD 1
 #endif
@@ -1754,15 +2063,15 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
             if constexpr (VAMP_WIDE_NODES && TAB) {
                 const unsigned long long wide_all = (unsigned long long)(flags & 0xffff);
                 if (VAMP_MID_NODES || wide_all) {
-                    if (guard) sweep_range_ff<MODE, PK, TAB, true, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
-                    else sweep_range_ff<MODE, PK, TAB, true, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
+                    if (guard) sweep_range_ff_any<MODE, PK, TAB, true, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
+                    else sweep_range_ff_any<MODE, PK, TAB, true, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
                 } else {
-                    if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
-                    else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                    if (guard) sweep_range_ff_any<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                    else sweep_range_ff_any<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
                 }
             } else {
-                if (guard) sweep_range_ff<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
-                else sweep_range_ff<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                if (guard) sweep_range_ff_any<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                else sweep_range_ff_any<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
             }
         } else if (TPIX > 1) sweep_range<MODE, PK, TPIX, TAB>(R, L, x, f, wt, lane, base0, full, stride, chi, tab);
         if constexpr (PK::TAIL || TPIX == 1)
@@ -2042,6 +2351,73 @@ __global__ __launch_bounds__(PK::THREADS, (min_waves<F32, PK>())) void k_lnprob(
     if (l == 0) {
         lnprob[w] = v;
         if (chi2) chi2[w] = chi;
+    }
+}
+
+// Test hook (vampdbg_node_sums): the node stage of every full tile of one region for one parameter vector, through the
+// device functions the fp64 far-field loop calls -- the classification and ff_node_pass for the full batches of a
+// wavefront's tiles, ff_classify_batch / ff_wide_nodes / ff_node_sums for what is left -- in the workgroup-per-walker
+// shape (wavefront j sweeps tile class j).  nodes[tile][16]; sets[first tile of a full batch][5] = {far, n6, n4, n3, wide}.
+template <int MODE>
+__global__ __launch_bounds__(PackSplit::THREADS) void k_dbg_node_sums(const RegionDev* __restrict__ regions, int region, PixPtrs px,
+                                                                      const double* __restrict__ theta, double* __restrict__ nodes,
+                                                                      unsigned* __restrict__ sets_out) {
+    using PK = PackSplit;
+    __shared__ typename PK::Lds lds[1];
+    __shared__ TileScratch scr[PK::WPB];
+    __shared__ alignas(16) double dct[ff_table_doubles<false>()];
+    __shared__ LineTables<table_doubles<false, MODE, PK>()> tabs[1];
+    ff_fill_table<false>(dct);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const RegionDev R = regions[region];
+    typename PK::Lds& L = lds[0];
+    if (wave == 0)
+        for (int d = lane; d < R.D; d += 64) L.theta[d] = theta[d];
+    group_barrier<PK>();
+    const double lp = stage_lines<MODE, PK, true, false, false, true>(R, L, lane, false, wave, tabs[0].a, px.x + R.pix_off);
+    if (!(lp > NEG_INF)) return;
+    TileScratch& Sx = scr[wave];
+    const double* tab = tabs[0].a;
+    const double2* geo = px.geo + (R.pix_off >> 8);
+    const int flags = __builtin_amdgcn_readfirstlane((int)(__double_as_longlong(L.theta[4 * PK::KCAP + 2]) & 0x3ffff));
+    const bool guard = (flags >> 16) != 0;
+    const unsigned wide_all = (unsigned)(flags & 0xffff);
+    constexpr int TILE = 64 * TPIX;
+    const int K = R.K, base1 = (R.P / TILE) * TILE, stride = PARTS * TILE;
+    const int base0 = __builtin_amdgcn_readfirstlane(wave * TILE);
+    int bfull = base0;
+#if VAMP_NODE_PASS_ON
+    const int ntile = base0 < base1 ? (base1 - base0 + stride - 1) / stride : 0;
+    bfull = __builtin_amdgcn_readfirstlane(base0 + (ntile / FF_BATCH) * (FF_BATCH * stride));
+    for (int batch = base0; batch < bfull; batch += FF_BATCH * stride) {
+        unsigned long long farmasks, widemasks, zonemasks;
+        NodeSets sets;
+        double mid, half;
+        ff_classify_batch_np<true, true>(L, geo, K, lane, batch, stride, wide_all, farmasks, widemasks, zonemasks, sets, mid, half);
+        const double fs = guard ? ff_node_pass<true, true>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets)
+                                : ff_node_pass<true, false>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets);
+        nodes[((batch + (lane >> 4) * stride) >> 8) * FF_NODES + (lane & (FF_NODES - 1))] = fs;
+        if (lane == 0) {
+            unsigned* so = sets_out + (batch >> 8) * 5;
+            so[0] = sets.far, so[1] = sets.n6, so[2] = sets.n4, so[3] = sets.n3, so[4] = sets.wide;
+        }
+    }
+#endif
+    for (int batch = bfull; batch < base1; batch += FF_BATCH * stride) {
+        unsigned long long farmasks, widemasks, zonemasks;
+        ff_classify_batch<true, false, true>(L, Sx, geo, K, lane, batch, base1, stride, wide_all, farmasks, widemasks, zonemasks);
+        for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX) {
+            const int base = batch + j * stride;
+            if (base >= base1) break;
+            const double2 tg = geo[base >> 8];
+            const double mid = tg.x, half = fabs(tg.y);
+            const int nfar = __builtin_popcount((unsigned)farmasks & 0xffffu), nwide = __builtin_popcount((unsigned)widemasks & 0xffffu);
+            const double fs_wide = nwide > 0 ? ff_wide_nodes<typename PK::Lds>(L, Sx.widelist[j], dct, tab, lane, nwide, mid, half) : 0.0;
+            const double fs = guard ? ff_node_sums<typename PK::Lds, true>(L, Sx.farlist[j], dct, lane, nfar, mid, half, fs_wide)
+                                    : ff_node_sums<typename PK::Lds, false>(L, Sx.farlist[j], dct, lane, nfar, mid, half, fs_wide);
+            if (lane < FF_NODES) nodes[(base >> 8) * FF_NODES + lane] = fs;
+        }
+        __builtin_amdgcn_wave_barrier();      // (the next batch's lists overwrite these)
     }
 }
 
@@ -3469,6 +3845,41 @@ long long vampdbg_tile_moments(vamp_ctx* c, double* out) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (out) HIP_TRY(hipMemcpy(out, c->mom_d.get(), slots * MOM_TILE * sizeof(double), hipMemcpyDeviceToHost));
     return MOM_TILE;
+}
+
+// Test hook, not part of the header: the far-field node stage of every full tile of `region` at the parameter vector
+// theta [D] (k_dbg_node_sums): nodes [tiles x 16] = the optical depth of the tile's far, mid and wide lines at its 16
+// Chebyshev nodes, sets [tiles x 5] = {far, n6, n4, n3, wide} at the first tile of every batch the line-major pass took
+// (ff_node_pass) and 0xffffffff elsewhere.  Returns the number of full tiles, 0 when the context runs no fp64 far field
+// (fp32, Gaussian lines, no full tile, more than 16 lines), or an error code.
+long long vampdbg_node_sums(vamp_ctx* c, int region, const double* theta, double* nodes, unsigned* sets) {
+    if (!c || !theta || !nodes || !sets) return fail(VAMP_ERR_ARG, "vampdbg_node_sums: bad argument");
+    if (c->regions_h.empty()) return fail(VAMP_ERR_STATE, "vampdbg_node_sums: call vamp_set_regions first");
+    if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vampdbg_node_sums: no such region");
+    const RegionDev& R = c->regions_h[region];
+    const long long tiles = R.P / (64 * TPIX);
+    if (c->f32 || c->mode == VAMP_GAUSS3 || !c->geo_d || tiles == 0 || R.K > KMAX) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<double> th_d, nodes_d;
+    DevBuf<unsigned> sets_d;
+    HIP_TRY(th_d.ensure(R.D));
+    HIP_TRY(nodes_d.ensure(tiles * FF_NODES));
+    HIP_TRY(sets_d.ensure(tiles * 5));
+    HIP_TRY(hipMemcpy(th_d.get(), theta, R.D * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(nodes_d.get(), 0, tiles * FF_NODES * sizeof(double)));
+    HIP_TRY(hipMemset(sets_d.get(), 0xff, tiles * 5 * sizeof(unsigned)));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->mode == VAMP_VOIGT4)
+        hipLaunchKernelGGL((k_dbg_node_sums<VAMP_VOIGT4>), dim3(1), dim3(PackSplit::THREADS), 0, c->stream, c->regions_d.get(), region, c->pix(),
+                           th_d.get(), nodes_d.get(), sets_d.get());
+    else
+        hipLaunchKernelGGL((k_dbg_node_sums<VAMP_NBZ3>), dim3(1), dim3(PackSplit::THREADS), 0, c->stream, c->regions_d.get(), region, c->pix(),
+                           th_d.get(), nodes_d.get(), sets_d.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(nodes, nodes_d.get(), tiles * FF_NODES * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sets, sets_d.get(), tiles * 5 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return tiles;
 }
 
 int vamp_version(void) { return VAMP_ABI_VERSION; }
