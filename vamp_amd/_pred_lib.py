@@ -1,0 +1,28 @@
+"""ctypes binding of libvamp_pred.so (include/vamp_pred.h): the pointwise predictive density and WAIC.
+
+Loading, the torch-order warning and the error check are ``_sidelib``'s, and so are their rules.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+from . import _sidelib
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvamp_pred.so")
+
+# name -> (restype, argtypes); mirrors include/vamp_pred.h one to one
+SIGNATURES = {
+    "vamp_pred_version": (C.c_int, []),
+    "vamp_pred_last_error": (C.c_char_p, []),
+    "vamp_pred_pointwise": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_int32)] * 4
+                            + [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]
+                            + [C.POINTER(C.c_double)] * 7 + [C.POINTER(C.c_int32)] * 3),
+}
+
+
+class PredError(RuntimeError):
+    pass
+
+
+bind, load, check = _sidelib.loader(__name__, "pred", PredError)

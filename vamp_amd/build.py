@@ -47,6 +47,13 @@ EVID_DEPS = [EVID_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_
              os.path.join(HERE, "..", "include", "vamp_evid.h")]
 EVID_FLAGS = SIDE_FLAGS
 
+# libvamp_pred.so (include/vamp_pred.h): the pointwise predictive density and WAIC, a fifth library on the same terms;
+# it shares the evaluator (voigt_math.hpp) with the main library
+PRED_SRC = os.path.join(HERE, "csrc", "predictive.hip")
+PRED_OUT = os.path.join(HERE, "libvamp_pred.so")
+PRED_DEPS = [PRED_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "..", "include", "vamp_pred.h")]
+PRED_FLAGS = SIDE_FLAGS
+
 
 def _compile(out, src, deps, flags, force, verbose):
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
@@ -76,11 +83,18 @@ def build_evid(force=False, verbose=True, out=None, defines=()):
     return _compile(out or EVID_OUT, EVID_SRC, EVID_DEPS, EVID_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
+def build_pred(force=False, verbose=True, out=None, defines=()):
+    """libvamp_pred.so; returns its path.  ``out`` / ``defines``: a variant build beside it (tools/bench_pred.py
+    compares the orientations of the scratch and the 16-lane form)."""
+    return _compile(out or PRED_OUT, PRED_SRC, PRED_DEPS, PRED_FLAGS + ["-D" + d for d in defines], force, verbose)
+
+
 def build(force=False, verbose=True):
-    """The four libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
+    """The five libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
     build_diag(force=force, verbose=verbose)
     build_post(force=force, verbose=verbose)
     build_evid(force=force, verbose=verbose)
+    build_pred(force=force, verbose=verbose)
     return _compile(OUT, SRC, DEPS, FLAGS, force, verbose)
 
 

@@ -82,6 +82,7 @@ class _EnsembleMCMC:
         self._thin = 1             # sampler steps per kept sample
         self._diag = None          # ChainDiagnostics of the device-unit chain, computed once
         self._post = {}            # probs -> PosteriorSummary of the device-unit chain at unit pixel width
+        self._pred = None          # PredictiveRecord of the device-unit chain, computed once
 
     def sample(self, iter, burn=0, thin=1, progress_bar=False, **_ignored):
         self._fit._run_sampler(int(iter), int(burn), int(thin))
@@ -176,6 +177,24 @@ class _EnsembleMCMC:
         return {"EW": rec(r.ew_mean, r.ew_sd, r.ew_q),
                 "components": [rec(r.comp_ew_mean[k], r.comp_ew_sd[k], r.comp_ew_q[k]) for k in range(len(r.comp_ew_mean))],
                 "pixel_width": width, "n_used": r.n_used, "n_bad": r.n_bad}
+
+
+    def waic(self):
+        """The fit's ``PredictiveRecord`` (vamp_amd.predictive): the pointwise log predictive density of the data under the
+        kept samples of the whole ensemble, ``elpd_waic`` with its standard error, ``p_waic`` and ``waic`` = -2 elpd_waic,
+        in the fit's pixel order.  One GPU call, cached per fit."""
+        if self._pred is None:
+            fit = self._fit
+            if fit._chain_dev is None:
+                raise RuntimeError("no chain: run the sampler first")
+            from . import predictive
+            _, recs = predictive.fits_predictive([fit], device=fit.device)
+            if self._pred is None:             # (fits_predictive fills the cache)
+                self._set_predictive(recs[0])
+        return self._pred
+
+    def _set_predictive(self, record):
+        self._pred = record
 
 
 class _Stats(Mapping):
@@ -495,6 +514,7 @@ class VPfit():
         mc_._flat, mc_._names, mc_._derived = flat, list(self._names), {}
         mc_._thin, mc_._diag = max(1, int(thin)), None
         mc_._post = {}
+        mc_._pred = None
         if self._voigt:      # the reference's callers ask for est_sigma_k in Voigt mode too (vpspectrum.py:400)
             for k in range(self._n):
                 mc_._derived["est_sigma_%d" % k] = ("est_G_%d" % k, self.GaussianWidth)

@@ -480,6 +480,36 @@ class VPspectrum():
         h5min.write(path, {k: np.array(v) for k, v in ev.items()})
         return path
 
+    def predictive(self, scratch_bytes=0):
+        """After ``fit_spectrum`` (batched or not): the pointwise log predictive density and WAIC of every kept fit from
+        ONE GPU call over their chains (vamp_amd.predictive).  A dict: ``lppd`` / ``ll_mean`` / ``p_waic_pix`` / ``elpd``
+        [n_pixels] in wavelength order (flipped like ``_harvest``; NaN outside regions), and per region ``elpd_waic`` /
+        ``elpd_se`` / ``p_waic`` / ``waic`` / ``lnl_mean`` / ``n_high`` / ``n_used`` / ``n_bad`` / ``n_comp`` /
+        ``time_step`` [n_regions]."""
+        from . import predictive
+        npx, regs = len(self.flux_array), self.regions
+        have, recs = predictive.fits_predictive([r.fit for r in regs], device=getattr(self, "device", 0), scratch_bytes=scratch_bytes)
+        if len(have) != len(regs):
+            raise RuntimeError("predictive: %d of %d regions have no chain" % (len(regs) - len(have), len(regs)))
+        out = {k: np.full(npx, np.nan) for k in ("lppd", "ll_mean", "p_waic_pix", "elpd")}
+        for k in ("elpd_waic", "elpd_se", "p_waic", "waic", "lnl_mean"):
+            out[k] = np.array([getattr(r, k) for r in recs], dtype=np.float64)
+        for k in ("n_high", "n_used", "n_bad"):
+            out[k] = np.array([getattr(r, k) for r in recs], dtype=np.int32)
+        out["n_comp"] = np.array([r.fit._n for r in regs], dtype=np.int32)
+        out["time_step"] = np.array([r.step for r in recs], dtype=np.int32)
+        for (start, end), r in zip(self.region_pixels, recs):
+            for k in ("lppd", "ll_mean", "p_waic_pix", "elpd"):
+                out[k][start:end] = np.flip(getattr(r, k), 0)
+        return out
+
+    def write_predictive(self, pred):
+        """``predictive()``'s dict as ``<prefix>predictive.h5`` through vamp_amd/h5min.py; returns the path"""
+        from . import h5min
+        path = self.output_filename + 'predictive.h5'
+        h5min.write(path, {k: np.array(v) for k, v in pred.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
