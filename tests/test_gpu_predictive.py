@@ -191,6 +191,25 @@ def test_packing_and_group_order_do_not_change_a_bit():
         _check(rec, g, "three groups, P=%d" % g["x"].size)
 
 
+def test_scratch_of_exactly_one_column_of_the_largest_group():
+    """S = 20, 17, 20 on P = 3, 1, 2 under scratch_bytes = 8 * 20: six passes of one column each, the S = 17 group in a
+    pass that has 3 doubles to spare, a group boundary on every pass boundary (the plan: tests/test_chain_groups.py);
+    every output equals the default-scratch call's bit for bit, and one byte less is an error"""
+    rng = np.random.default_rng(67)
+    groups = [_group(rng, 3, 1, vo.MODE_GAUSS3, 5, 4, sd=0), _group(rng, 1, 2, vo.MODE_VOIGT4, 17, 1, sd=1),
+              _group(rng, 2, 2, vo.MODE_GAUSS3, 10, 2, sd=0, descending=True)]
+    assert [g["chain"].shape[0] * g["chain"].shape[1] for g in groups] == [20, 17, 20]
+    one = _run(groups)
+    for a, b in zip(one, _run(groups, scratch_bytes=8 * 20)):
+        _identical(a, b)
+    for g, rec in zip(groups, one):
+        _check(rec, g, "one column per pass, P=%d" % g["x"].size)
+        assert rec.n_bad == 0
+    from vamp_amd._pred_lib import PredError
+    with pytest.raises(PredError, match="less than one column"):
+        _run(groups, scratch_bytes=8 * 20 - 1)
+
+
 def test_every_output_alone():
     """each output with every other pointer NULL equals the full call's; the group sums are formed also when the
     per-pixel outputs are not asked for"""

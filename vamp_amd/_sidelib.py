@@ -1,5 +1,6 @@
-"""What the ctypes bindings of the side libraries (``_diag_lib``, ``_post_lib``, ``_evid_lib``) and their callers
-(``diagnostics``, ``posterior``, ``evidence``) share.
+"""What the ctypes bindings of the side libraries (``_diag_lib``, ``_post_lib``, ``_evid_lib``, ``_pred_lib``) and
+their callers (``diagnostics``, ``posterior``, ``evidence``, ``predictive``) share; the second half is what the two
+callers that walk every sample of a chain (``posterior``, ``predictive``) hand their libraries alike.
 
 The rules of a binding are those of ``_lib``: no fallback (a missing library raises, every call needs a GPU), and
 the library is loaded after torch so that it binds the ROCm runtime torch has mapped -- the one libvamp_hip.so binds
@@ -16,6 +17,7 @@ import warnings
 import numpy as np
 
 Q_OF_MODE = {0: 3, 1: 4}      # parameters per line: GAUSS3, VOIGT4
+MAX_CHAIN_SAMPLES = 16384     # VAMP_POST_MAX_SAMPLES of include/vamp_post.h, VAMP_PRED_MAX_SAMPLES of include/vamp_pred.h
 
 
 def loader(module, stem, error):
@@ -74,3 +76,53 @@ def fits_with_chain(fits):
     """the ``VPfit`` objects that have been sampled and still hold their device-unit chain"""
     return [f for f in fits if getattr(getattr(f, "mcmc", None), "_fit", None) is not None
             and getattr(f, "_chain_dev", None) is not None]
+
+
+# ---- the chain arguments of vamp_post_summaries and vamp_pred_pointwise ------------------------------------------
+def per_group(v, G, cast):
+    """one value for all ``G`` groups, or one per group"""
+    return [cast(v)] * G if np.isscalar(v) else [cast(e) for e in v]
+
+
+def time_step(n_keep, walkers):
+    """the smallest step s for which every s-th of ``n_keep`` kept samples of ``walkers`` walkers fits the libraries:
+    ceil(n_keep / s) * walkers <= MAX_CHAIN_SAMPLES"""
+    if walkers > MAX_CHAIN_SAMPLES:
+        raise ValueError(f"an ensemble of {walkers} walkers exceeds the {MAX_CHAIN_SAMPLES} samples the library takes")
+    rows = MAX_CHAIN_SAMPLES // walkers
+    step = max(1, -(-n_keep // rows))
+    while -(-n_keep // step) > rows:
+        step += 1
+    return step
+
+
+def check_chain_shapes(arrays, n_comp, modes, sds, notes):
+    """every chain is [N, W, D] with the D of its lines and mode; ``notes[g]`` closes the message"""
+    for a, k, m, sd, note in zip(arrays, n_comp, modes, sds, notes):
+        if a.ndim != 3:
+            raise ValueError("every chain must be an [N, W, D] array")
+        if m in Q_OF_MODE and a.shape[2] != Q_OF_MODE[m] * k + sd:
+            raise ValueError(f"a chain of {a.shape[2]} parameters does not hold {k} lines of mode {m} ({note})")
+
+
+def host_layout(arrays, steps):
+    """(bases, ld, n_keep, walkers) of contiguous fp64 [N, W, D] host arrays, every ``steps[g]``-th time read in place"""
+    return ([a.ctypes.data for a in arrays], [a.shape[1] * a.shape[2] * s for a, s in zip(arrays, steps)],
+            [-(-a.shape[0] // s) for a, s in zip(arrays, steps)], [a.shape[1] for a in arrays])
+
+
+def context_layout(ctx, chain_ptr, n_keep):
+    """(n_comp, modes, sample_sd, bases, ld, n_keep, walkers) of the regions of the device chain ``HipContext.run_dev``
+    wrote at ``chain_ptr``"""
+    R, mode = len(ctx.ndims), int(ctx.mode)
+    ks = [int(k) for k in ctx.n_comp]
+    sds = [d - Q_OF_MODE.get(mode, 3) * k for d, k in zip(ctx.ndims, ks)]
+    return ks, [mode] * R, sds, region_bases(ctx, chain_ptr), [ctx.total_theta] * R, [int(n_keep)] * R, [int(ctx.W)] * R
+
+
+def chain_args(n_pix, n_comp, modes, sample_sd, bases, is_device, ld, n_keep, walkers):
+    """the arguments n_pix .. walkers of both entry points, in the headers' order, as ctypes takes them (a pointer keeps
+    its array alive)"""
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
+    return [i32(n_pix), i32(n_comp), i32(modes), i32(sample_sd), (C.c_void_p * len(bases))(*[int(b) for b in bases]),
+            int(bool(is_device)), np.ascontiguousarray(ld, dtype=np.int64).ctypes.data_as(C.POINTER(C.c_int64)), i32(n_keep), i32(walkers)]

@@ -19,25 +19,27 @@ DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("ff_matrix.inc", "ff_mat
 # (profiles/r03_b_f32_variants.txt; MI355X_MICROARCH.md lists packed fp32 VALU as an anti-lever).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-shared", "-fPIC"]
 
-# The three side libraries share their flags, the frame of their entry points (side_call.hpp) and -- the posterior and
-# the evidence -- the lane-group evaluator (lane_group.hpp): an edit of a shared header rebuilds what includes it
+# The four side libraries share their flags, the frame of their entry points (side_call.hpp) and -- all but the
+# diagnostics -- the lane-group evaluator (lane_group.hpp); the posterior and the predictive density also the chain
+# checks and the pass planner (chain_groups.hpp): an edit of a shared header rebuilds what includes it
 SIDE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
+POST_FLAGS = EVID_FLAGS = PRED_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
 SIDE_CALL = os.path.join(HERE, "csrc", "side_call.hpp")
 LANE_GROUP = os.path.join(HERE, "csrc", "lane_group.hpp")
+CHAIN_GROUPS = os.path.join(HERE, "csrc", "chain_groups.hpp")
 
 # libvamp_diag.so (include/vamp_diag.h): the chain diagnostics, a library of its own with its own dependency list,
 # so that an edit of chain_diag.hip rebuilds it in seconds and leaves the main library alone
 DIAG_SRC = os.path.join(HERE, "csrc", "chain_diag.hip")
 DIAG_OUT = os.path.join(HERE, "libvamp_diag.so")
 DIAG_DEPS = [DIAG_SRC, SIDE_CALL, os.path.join(HERE, "..", "include", "vamp_diag.h")]
-DIAG_FLAGS = SIDE_FLAGS
 
 # libvamp_post.so (include/vamp_post.h): the posterior summaries, a third library on the same terms; it shares
 # voigt_math.hpp with the main library, so an edit of the evaluator rebuilds both
 POST_SRC = os.path.join(HERE, "csrc", "posterior.hip")
 POST_OUT = os.path.join(HERE, "libvamp_post.so")
-POST_DEPS = [POST_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "..", "include", "vamp_post.h")]
-POST_FLAGS = SIDE_FLAGS
+POST_DEPS = [POST_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, os.path.join(HERE, "csrc", "voigt_math.hpp"),
+             os.path.join(HERE, "..", "include", "vamp_post.h")]
 
 # libvamp_evid.so (include/vamp_evid.h): the log-evidence from tempered ensembles, a fourth library on the same terms;
 # it shares the evaluator (voigt_math.hpp) and the draws (draws.hpp) with the main library
@@ -45,14 +47,13 @@ EVID_SRC = os.path.join(HERE, "csrc", "evidence.hip")
 EVID_OUT = os.path.join(HERE, "libvamp_evid.so")
 EVID_DEPS = [EVID_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "csrc", "draws.hpp"),
              os.path.join(HERE, "..", "include", "vamp_evid.h")]
-EVID_FLAGS = SIDE_FLAGS
 
 # libvamp_pred.so (include/vamp_pred.h): the pointwise predictive density and WAIC, a fifth library on the same terms;
 # it shares the evaluator (voigt_math.hpp) with the main library
 PRED_SRC = os.path.join(HERE, "csrc", "predictive.hip")
 PRED_OUT = os.path.join(HERE, "libvamp_pred.so")
-PRED_DEPS = [PRED_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "..", "include", "vamp_pred.h")]
-PRED_FLAGS = SIDE_FLAGS
+PRED_DEPS = [PRED_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, os.path.join(HERE, "csrc", "voigt_math.hpp"),
+             os.path.join(HERE, "..", "include", "vamp_pred.h")]
 
 
 def _compile(out, src, deps, flags, force, verbose):
@@ -68,25 +69,25 @@ def _compile(out, src, deps, flags, force, verbose):
 
 def build_diag(force=False, verbose=True):
     """libvamp_diag.so; returns its path"""
-    return _compile(DIAG_OUT, DIAG_SRC, DIAG_DEPS, DIAG_FLAGS, force, verbose)
+    return _compile(DIAG_OUT, DIAG_SRC, DIAG_DEPS, SIDE_FLAGS, force, verbose)
 
 
 def build_post(force=False, verbose=True, out=None, defines=()):
     """libvamp_post.so; returns its path.  ``out`` / ``defines``: a variant build beside it (tools/bench_post.py
     compares the orientations of the scratch and the 16-lane form)."""
-    return _compile(out or POST_OUT, POST_SRC, POST_DEPS, POST_FLAGS + ["-D" + d for d in defines], force, verbose)
+    return _compile(out or POST_OUT, POST_SRC, POST_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
 def build_evid(force=False, verbose=True, out=None, defines=()):
     """libvamp_evid.so; returns its path.  ``out`` / ``defines``: a variant build beside it (tools/bench_evid.py
     compares the lane widths)."""
-    return _compile(out or EVID_OUT, EVID_SRC, EVID_DEPS, EVID_FLAGS + ["-D" + d for d in defines], force, verbose)
+    return _compile(out or EVID_OUT, EVID_SRC, EVID_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
 def build_pred(force=False, verbose=True, out=None, defines=()):
     """libvamp_pred.so; returns its path.  ``out`` / ``defines``: a variant build beside it (tools/bench_pred.py
     compares the orientations of the scratch and the 16-lane form)."""
-    return _compile(out or PRED_OUT, PRED_SRC, PRED_DEPS, PRED_FLAGS + ["-D" + d for d in defines], force, verbose)
+    return _compile(out or PRED_OUT, PRED_SRC, PRED_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
 def build(force=False, verbose=True):

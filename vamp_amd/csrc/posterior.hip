@@ -2,7 +2,7 @@
 // (include/vamp_post.h, libvamp_post.so).  Definitions: DESIGN.md "Posterior summaries".
 //
 // The work is a list of items (group, pixel range), packed greedily into passes whose flux scratch fits
-// scratch_bytes.  Two launches per pass:
+// scratch_bytes (chain_groups.hpp, which predictive.hip shares).  Two launches per pass:
 //   k_post_eval    one workgroup per (item, 64 samples).  A wavefront -- or, for short regions of few lines, a
 //                  16-lane group -- owns a sample: its parameters become line records once (centre, scale,
 //                  damping, amplitude factor, pole factor, h y and the 44-entry near-axis table of voigt_math.hpp, in
@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/vamp_post.h"
+#include "chain_groups.hpp"
 #include "lane_group.hpp"
 #include "side_call.hpp"
 #include "voigt_math.hpp"
@@ -53,8 +54,6 @@ constexpr int kEvalWaves = kEvalBlock / 64;
 constexpr int kSamplesPerBlock = 64;
 constexpr int kRec = 6;                    // doubles of a line record
 constexpr int kColBlock = 1024;            // one size for every column: the reduction order must not depend on the pass
-constexpr long long kDefaultScratch = 256ll << 20;
-constexpr double SQRT_LN2 = 0.83255461115769775635;
 
 // LDS of one sample: line records, near-axis tables, and the [K + 1][lanes + 1] tile the decrements cross lanes in
 // (rows padded by one: the summing lanes read down a column each)
@@ -84,25 +83,22 @@ struct ColSet {                    // columns that share a source matrix
     int S, n2;                     // n2: S rounded up to a power of two
 };
 
-// The group geometry, the table fill and the optical depth of a line are written out here, not taken from
-// lane_group.hpp: through the header's functions the compiler orders this kernel's loads differently and renumbers
-// its registers (code 8472 -> 8488 bytes; 128 VGPRs, 100 SGPRs, occupancy 4, no scratch either way), and that form has
-// not been timed or compared bit for bit on a device.  eval_point of evidence.hip compiles to the same code both ways.
 __global__ __launch_bounds__(kEvalBlock) void k_post_eval(const Item* __restrict__ items, const int2* __restrict__ tasks,
                                                           int region_doubles) {
     extern __shared__ double lds[];
     const int2 task = tasks[blockIdx.x];
     const Item I = items[task.x];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int lanes = I.lanes, nsub = 64 / lanes;
-    const int sub = lane / lanes, gl = lane - sub * lanes;
+    const int lanes = I.lanes;
+    const vamp::LaneGroup lg = vamp::lane_group(lane, lanes);
+    const int nsub = lg.nsub, sub = lg.sub, gl = lg.gl;
     const int K = I.K, row = lanes + 1;
     double* rec = lds + (size_t)wave * region_doubles + (size_t)sub * slot_doubles(K, lanes);
     double* dtab = rec + K * kRec;
     double* tile = dtab + K * vamp::DTAB_N;
     const int s_end = min(task.y + kSamplesPerBlock, I.S);
     const bool voigt = I.q == 4;
-    const unsigned long long gmask = (lanes == 64 ? ~0ull : ((1ull << lanes) - 1ull)) << (sub * lanes);
+    const unsigned long long gmask = vamp::group_mask(lanes, sub);
 
     for (int sb = task.y + wave * nsub; sb < s_end; sb += kEvalWaves * nsub) {      // (uniform per wavefront)
         const int s = sb + sub;
@@ -111,35 +107,13 @@ __global__ __launch_bounds__(kEvalBlock) void k_post_eval(const Item* __restrict
         bool bad_lane = false;
         if (valid && gl < K) {
             const int t = s / I.W, w = s - t * I.W;
-            const double* th = I.chain + (long long)t * I.ld + (long long)w * I.D + I.q * gl;
-            const double a = th[0], c = th[1];
-            double* r = rec + gl * kRec;
-            r[0] = c;
-            if (voigt) {
-                const double Lw = th[2], G = th[3];
-                bad_lane = !(isfinite(a) && isfinite(c) && isfinite(Lw) && isfinite(G)) || G <= 0.0 || Lw < 0.0;
-                const double rG = vamp::rcp_nr(G);
-                const double y = (Lw * SQRT_LN2) * rG;
-                r[1] = (2.0 * SQRT_LN2) * rG;
-                r[2] = y;
-                r[3] = a * y;                      // tau_k = A y sqrt(pi) H: the evaluator returns sqrt(pi) H
-                r[4] = vamp::core_pole_factor(y);
-                r[5] = vamp::core_hy(y);
-            } else {
-                const double sg = th[2];
-                bad_lane = !(isfinite(a) && isfinite(c) && isfinite(sg)) || sg <= 0.0;
-                r[1] = 1.0 / sg; r[2] = 0.0; r[3] = a; r[4] = 0.0; r[5] = 0.0;
-            }
+            bad_lane = vamp::line_record(voigt, I.chain + (long long)t * I.ld + (long long)w * I.D + I.q * gl, rec + gl * kRec);
         }
         const bool bad = (__ballot(bad_lane) & gmask) != 0ull;
         const bool good = valid && !bad;
         if (valid && gl == 0) I.bad[s] = bad ? 1 : 0;
         lds_fence();
-        if (good && voigt)
-            for (int e = gl; e < K * vamp::DTAB_N; e += lanes) {
-                const int k = e / vamp::DTAB_N, n = e - k * vamp::DTAB_N;
-                dtab[e] = vamp::core_dtab_entry(n, rec[k * kRec + 2]);
-            }
+        if (good && voigt) vamp::fill_dtab<kRec>(dtab, rec, K, gl, lanes);
         lds_fence();
         // 2. the item's pixels, a round of `lanes` at a time; lanes 0 .. K keep the running sums
         const bool owner = good && gl <= K;
@@ -151,15 +125,7 @@ __global__ __launch_bounds__(kEvalBlock) void k_post_eval(const Item* __restrict
                 const double xi = I.x[p];
                 double tau = 0.0;
                 for (int k = 0; k < K; ++k) {
-                    const double* r = rec + k * kRec;
-                    double tk;
-                    if (voigt) {
-                        const double X = fabs(xi - r[0]) * r[1];
-                        tk = r[3] * vamp::voigt_Hs(X, r[2], dtab + k * vamp::DTAB_N, r[4], r[5]);
-                    } else {
-                        const double u = (xi - r[0]) * r[1];
-                        tk = r[3] * exp(-0.5 * (u * u));
-                    }
+                    const double tk = vamp::line_tau(voigt, xi, rec + k * kRec, dtab + k * vamp::DTAB_N);
                     tile[k * row + gl] = 1.0 - exp(-tk);
                     tau += tk;
                 }
@@ -252,8 +218,7 @@ __global__ __launch_bounds__(kColBlock) void k_post_column(const ColSet* __restr
 constexpr size_t kColMaxLds = (size_t)VAMP_POST_MAX_SAMPLES * sizeof(double);
 constexpr size_t kEvalMaxLds = (size_t)kEvalWaves * slot_doubles(VAMP_POST_MAX_COMPONENTS, 64) * sizeof(double);
 struct Pass {
-    size_t item0, item1;           // its items
-    size_t etask0, etask1;         // its k_post_eval workgroups
+    size_t etask0, etask1;        // its k_post_eval workgroups
     size_t ctask0, ctask1;         // its k_post_column workgroups
     int region_doubles = 0;        // LDS of a wavefront of k_post_eval
     int n2 = 1;                    // longest column
@@ -281,43 +246,20 @@ VAMP_POST_API int vamp_post_summaries(int device, void* hip_stream, int n_groups
         return fail(fn + "n_probs = " + std::to_string(n_probs) + " is outside 1 .. " + std::to_string(VAMP_POST_MAX_PROBS));
     for (int i = 0; i < n_probs; ++i)
         if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return fail(fn + "probs[" + std::to_string(i) + "] is outside [0, 1]");
-    if (scratch_bytes < 0) return fail(fn + "scratch_bytes must not be negative");
     const int Q = n_probs;
-    std::vector<int> Sg(n_groups), Dg(n_groups);
-    long long tot_pix = 0, tot_comp = 0, tot_ew = 0, tot_s = 0;
-    int s_max = 0;
+    ChainGroups cg;
+    const std::string err = check_chain_groups(fn, n_groups, x, n_pix, n_comp, mode, sample_sd, base, ld, n_keep, walkers, scratch_bytes,
+                                               VAMP_POST_MAX_SAMPLES, VAMP_POST_MAX_COMPONENTS,
+                                               "a column must fit the LDS; subsample in time: ld * step, ceil(n_keep / step)", cg);
+    if (!err.empty()) return fail(err);
+    const long long tot_pix = cg.tot_pix, tot_s = cg.tot_s;
+    long long tot_comp = 0, tot_ew = 0;
     for (int g = 0; g < n_groups; ++g) {
-        const std::string at = fn + "group " + std::to_string(g) + ": ";
-        if (!base[g]) return fail(at + "NULL base pointer");
-        if (!x[g]) return fail(at + "NULL abscissa");
-        if (n_pix[g] <= 0) return fail(at + "n_pix must be positive");
-        if (n_comp[g] < 1 || n_comp[g] > VAMP_POST_MAX_COMPONENTS)
-            return fail(at + "n_comp = " + std::to_string(n_comp[g]) + " is outside 1 .. " + std::to_string(VAMP_POST_MAX_COMPONENTS));
-        if (mode[g] == 2) return fail(at + "mode 2 (NBZ3) is not supported: pass the chain in the GAUSS3 (0) or VOIGT4 (1) layout");
-        if (mode[g] != 0 && mode[g] != 1) return fail(at + "mode must be 0 (GAUSS3) or 1 (VOIGT4)");
-        if (sample_sd[g] != 0 && sample_sd[g] != 1) return fail(at + "sample_sd must be 0 or 1");
-        if (n_keep[g] <= 0 || walkers[g] <= 0) return fail(at + "n_keep and walkers must be positive");
-        const long long S = (long long)n_keep[g] * walkers[g];
-        if (S > VAMP_POST_MAX_SAMPLES)
-            return fail(at + "n_keep * walkers = " + std::to_string(S) + " exceeds " + std::to_string(VAMP_POST_MAX_SAMPLES) +
-                        " (a column must fit the LDS; subsample in time: ld * step, ceil(n_keep / step))");
-        Dg[g] = (mode[g] == 1 ? 4 : 3) * n_comp[g] + sample_sd[g];
-        if (ld[g] < (int64_t)walkers[g] * Dg[g]) return fail(at + "ld < walkers * ndim");
-        if (!std::isfinite(pixel_width[g])) return fail(at + "pixel_width is not finite");
-        for (int p = 0; p < n_pix[g]; ++p)
-            if (!std::isfinite(x[g][p])) return fail(at + "the abscissa is not finite at pixel " + std::to_string(p));
-        Sg[g] = (int)S;
-        s_max = Sg[g] > s_max ? Sg[g] : s_max;
-        tot_pix += n_pix[g];
+        if (!std::isfinite(pixel_width[g])) return fail(fn + "group " + std::to_string(g) + ": pixel_width is not finite");
         tot_comp += n_comp[g];
-        tot_ew += S * (n_comp[g] + 1);
-        tot_s += S;
+        tot_ew += (long long)cg.S[g] * (n_comp[g] + 1);
     }
     if (tot_pix * Q > (1LL << 31) || tot_pix > (1LL << 30)) return fail(fn + "too many outputs");
-    const long long cap = (scratch_bytes ? scratch_bytes : kDefaultScratch) / (long long)sizeof(double);
-    if (cap < s_max)
-        return fail(fn + "scratch_bytes = " + std::to_string(scratch_bytes) + " is less than one column of the largest group (" +
-                    std::to_string((long long)s_max * (long long)sizeof(double)) + " bytes)");
 
     DeviceRestore restore;
     if (set_device(fn, device, restore)) return -1;
@@ -332,7 +274,7 @@ VAMP_POST_API int vamp_post_summaries(int device, void* hip_stream, int n_groups
     DevBuf staging;
     if (!is_device) {
         std::vector<long long> len(n_groups);
-        for (int g = 0; g < n_groups; ++g) len[g] = chain_span(n_keep[g], ld[g], walkers[g], Dg[g]);
+        for (int g = 0; g < n_groups; ++g) len[g] = chain_span(n_keep[g], ld[g], walkers[g], cg.D[g]);
         if (stage_chains(len, base, st, staging, dbase)) return -1;
     }
 
@@ -356,103 +298,77 @@ VAMP_POST_API int vamp_post_summaries(int device, void* hip_stream, int n_groups
         }
     }
 
-    // the plan: items packed greedily into passes; a group that does not fit what is left of a pass is split over
-    // pixel ranges; the K + 1 equivalent-width columns of a group follow its last range
+    // the plan (chain_groups.hpp): one item and one column set per range; the K + 1 equivalent-width columns of a
+    // group follow its last range, in that range's pass: they run after the k_post_eval that completes their sums
+    const PassPlan plan = plan_passes(cg.cap, cg.S, n_pix, n_groups);
+    const long long scratch_len = plan.scratch_len;
+    HIP_TRY(hipMalloc(&d_scratch.p, (size_t)scratch_len * sizeof(double)));
     std::vector<Item> items;
     std::vector<ColSet> sets;
     std::vector<int2> etasks, ctasks;
-    std::vector<Pass> passes;
-    std::vector<long long> item_scratch, set_scratch;    // offset into the pass's scratch (a set off the scratch: -1)
-    long long scratch_len = 0;
-    {
-        Pass cur{};
-        long long used = 0, pix_off = 0, ew_off = 0, s_off = 0, comp_off = 0;
-        auto close = [&]() {
-            cur.item1 = items.size(); cur.etask1 = etasks.size(); cur.ctask1 = ctasks.size();
-            if (cur.item1 > cur.item0) passes.push_back(cur);
-            scratch_len = used > scratch_len ? used : scratch_len;
-            cur = Pass{};
-            cur.item0 = items.size(); cur.etask0 = etasks.size(); cur.ctask0 = ctasks.size();
-            used = 0;
-        };
-        for (int g = 0; g < n_groups; ++g) {
-            const int S = Sg[g], K = n_comp[g], P = n_pix[g];
-            int n2 = 1;
-            while (n2 < S) n2 <<= 1;
-            const int lanes = vamp::group_lanes(VAMP_POST_NARROW, P, K);
-            const int region = (64 / lanes) * slot_doubles(K, lanes);
-            double* ew = dm + o_ew + ew_off;
-            uint8_t* bad = d_bad.as<uint8_t>() + s_off;
-            for (int p0 = 0; p0 < P;) {
-                const long long fit = (cap - used) / S;
-                if (fit == 0) { close(); continue; }              // (an empty pass holds at least one column: cap >= s_max)
-                const int np = (int)((long long)(P - p0) < fit ? (P - p0) : fit);
-                Item it;
-                it.chain = dbase[g];
-                it.x = dm + o_x + pix_off + p0;
-                it.flux = nullptr;                                 // (the scratch is allocated when its size is known)
-                it.ew = ew; it.bad = bad;
-                it.ld = ld[g];
-                it.fs_s = VAMP_POST_PIXEL_MAJOR ? 1 : np;
-                it.fs_p = VAMP_POST_PIXEL_MAJOR ? S : 1;
-                it.W = walkers[g]; it.D = Dg[g]; it.K = K; it.q = mode[g] == 1 ? 4 : 3;
-                it.S = S; it.np = np; it.p0 = p0; it.lanes = lanes;
-                ColSet cs;
-                cs.src = nullptr; cs.bad = bad;
-                cs.mean = dm + o_fm + pix_off + p0;
-                cs.sd = dm + o_fs + pix_off + p0;
-                cs.q = dm + o_fq + pix_off * Q + p0;
-                cs.counts = nullptr;
-                cs.stride_c = it.fs_p; cs.stride_s = it.fs_s; cs.q_qs = P; cs.q_cs = 1;
-                cs.scale = 1.0; cs.S = S; cs.n2 = n2;
-                item_scratch.push_back(used);
-                set_scratch.push_back(used);
-                const int ii = (int)items.size(), si = (int)sets.size();
-                items.push_back(it);
-                sets.push_back(cs);
-                for (int s0 = 0; s0 < S; s0 += kSamplesPerBlock) etasks.push_back(make_int2(ii, s0));
-                for (int c = 0; c < np; ++c) ctasks.push_back(make_int2(si, c));
-                cur.region_doubles = region > cur.region_doubles ? region : cur.region_doubles;
-                cur.n2 = n2 > cur.n2 ? n2 : cur.n2;
-                used += (long long)np * S;
-                p0 += np;
-            }
+    std::vector<Pass> passes(plan.first.size());
+    long long pix_off = 0, ew_off = 0, s_off = 0, comp_off = 0;      // of the range's group
+    for (const Range& r : plan.ranges) {
+        const int g = r.group, S = cg.S[g], K = n_comp[g], P = n_pix[g], p0 = r.p0, np = r.np;
+        int n2 = 1;
+        while (n2 < S) n2 <<= 1;
+        const int lanes = vamp::group_lanes(VAMP_POST_NARROW, P, K);
+        const int region = (64 / lanes) * slot_doubles(K, lanes);
+        Pass& ps = passes[r.pass];
+        if (r.offset == 0) { ps.etask0 = etasks.size(); ps.ctask0 = ctasks.size(); }
+        Item it;
+        it.chain = dbase[g];
+        it.x = dm + o_x + pix_off + p0;
+        it.flux = d_scratch.as<double>() + r.offset;
+        it.ew = dm + o_ew + ew_off; it.bad = d_bad.as<uint8_t>() + s_off;
+        it.ld = ld[g];
+        it.fs_s = VAMP_POST_PIXEL_MAJOR ? 1 : np;
+        it.fs_p = VAMP_POST_PIXEL_MAJOR ? S : 1;
+        it.W = walkers[g]; it.D = cg.D[g]; it.K = K; it.q = mode[g] == 1 ? 4 : 3;
+        it.S = S; it.np = np; it.p0 = p0; it.lanes = lanes;
+        ColSet cs;
+        cs.src = it.flux; cs.bad = it.bad;
+        cs.mean = dm + o_fm + pix_off + p0;
+        cs.sd = dm + o_fs + pix_off + p0;
+        cs.q = dm + o_fq + pix_off * Q + p0;
+        cs.counts = nullptr;
+        cs.stride_c = it.fs_p; cs.stride_s = it.fs_s; cs.q_qs = P; cs.q_cs = 1;
+        cs.scale = 1.0; cs.S = S; cs.n2 = n2;
+        const int ii = (int)items.size(), si = (int)sets.size();
+        items.push_back(it);
+        sets.push_back(cs);
+        for (int s0 = 0; s0 < S; s0 += kSamplesPerBlock) etasks.push_back(make_int2(ii, s0));
+        for (int c = 0; c < np; ++c) ctasks.push_back(make_int2(si, c));
+        ps.region_doubles = region > ps.region_doubles ? region : ps.region_doubles;
+        ps.n2 = n2 > ps.n2 ? n2 : ps.n2;
+        if (p0 + np == P) {
             ColSet comp;                                           // the lines' columns, then the region's
-            comp.src = ew; comp.bad = bad;
+            comp.src = it.ew; comp.bad = it.bad;
             comp.mean = dm + o_cm + comp_off; comp.sd = dm + o_cs + comp_off; comp.q = dm + o_cq + comp_off * Q;
             comp.counts = nullptr;
             comp.stride_c = 1; comp.stride_s = K + 1; comp.q_qs = 1; comp.q_cs = Q;
             comp.scale = pixel_width[g]; comp.S = S; comp.n2 = n2;
             ColSet tot = comp;
-            tot.src = ew + K;
+            tot.src = it.ew + K;
             tot.mean = dm + o_em + g; tot.sd = dm + o_es + g; tot.q = dm + o_eq + (long long)g * Q;
             tot.counts = d_counts.as<int32_t>() + 2 * g;
-            const int si = (int)sets.size();
             sets.push_back(comp);
             sets.push_back(tot);
-            set_scratch.push_back(-1);
-            set_scratch.push_back(-1);
-            for (int k = 0; k < K; ++k) ctasks.push_back(make_int2(si, k));
-            ctasks.push_back(make_int2(si + 1, 0));
+            for (int k = 0; k < K; ++k) ctasks.push_back(make_int2(si + 1, k));
+            ctasks.push_back(make_int2(si + 2, 0));
             pix_off += P; ew_off += (long long)S * (K + 1); s_off += S; comp_off += K;
         }
-        close();
+        ps.etask1 = etasks.size(); ps.ctask1 = ctasks.size();
     }
     if (etasks.size() > 0x7fffffff || ctasks.size() > 0x7fffffff) return fail(fn + "too many workgroups");
-    HIP_TRY(hipMalloc(&d_scratch.p, (size_t)scratch_len * sizeof(double)));
-    for (size_t i = 0; i < items.size(); ++i) items[i].flux = d_scratch.as<double>() + item_scratch[i];
-    for (size_t i = 0; i < sets.size(); ++i)
-        if (set_scratch[i] >= 0) sets[i].src = d_scratch.as<double>() + set_scratch[i];
 
     DevBuf d_items, d_sets, d_etasks, d_ctasks;
     if (upload(d_items, items, st) || upload(d_sets, sets, st) || upload(d_etasks, etasks, st) || upload(d_ctasks, ctasks, st)) return -1;
     for (const Pass& ps : passes) {
-        if (ps.etask1 > ps.etask0) {
-            hipLaunchKernelGGL(k_post_eval, dim3((unsigned)(ps.etask1 - ps.etask0)), dim3(kEvalBlock),
-                               (size_t)kEvalWaves * ps.region_doubles * sizeof(double), st, d_items.as<Item>(),
-                               d_etasks.as<int2>() + ps.etask0, ps.region_doubles);
-            HIP_TRY(hipGetLastError());
-        }
+        hipLaunchKernelGGL(k_post_eval, dim3((unsigned)(ps.etask1 - ps.etask0)), dim3(kEvalBlock),
+                           (size_t)kEvalWaves * ps.region_doubles * sizeof(double), st, d_items.as<Item>(),
+                           d_etasks.as<int2>() + ps.etask0, ps.region_doubles);
+        HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_post_column, dim3((unsigned)(ps.ctask1 - ps.ctask0)), dim3(kColBlock), (size_t)ps.n2 * sizeof(double), st,
                            d_sets.as<ColSet>(), d_ctasks.as<int2>() + ps.ctask0, d_probs.as<double>(), Q);
         HIP_TRY(hipGetLastError());
@@ -465,12 +381,5 @@ VAMP_POST_API int vamp_post_summaries(int device, void* hip_stream, int n_groups
         fetch(comp_ew_mean, dm + o_cm, tot_comp * sz, st) || fetch(comp_ew_sd, dm + o_cs, tot_comp * sz, st) ||
         fetch(comp_ew_q, dm + o_cq, tot_comp * Q * sz, st))
         return -1;
-    std::vector<int32_t> counts((size_t)n_groups * 2);
-    HIP_TRY(hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int g = 0; g < n_groups; ++g) {
-        if (n_used) n_used[g] = counts[2 * g];
-        if (n_bad) n_bad[g] = counts[2 * g + 1];
-    }
-    return 0;
+    return fetch_counts(d_counts, n_groups, n_used, n_bad, st);
 }

@@ -2,7 +2,7 @@
 // (include/vamp_pred.h, libvamp_pred.so).  Definitions: DESIGN.md "Pointwise predictive density and WAIC".
 //
 // The work is a list of items (group, pixel range), packed greedily into passes whose log-likelihood scratch fits
-// scratch_bytes, as posterior.hip packs its flux scratch.  Two launches per pass, one at the end:
+// scratch_bytes (chain_groups.hpp, which posterior.hip shares).  Two launches per pass, one at the end:
 //   k_pred_eval    one workgroup per (item, 64 samples).  A wavefront -- or, for short regions of few lines, a
 //                  16-lane group -- owns a sample: its parameters become line records and near-axis tables in LDS
 //                  once (lane_group.hpp), then its lanes walk the item's pixels and write the log-likelihood of the
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/vamp_pred.h"
+#include "chain_groups.hpp"
 #include "lane_group.hpp"
 #include "side_call.hpp"
 #include "voigt_math.hpp"
@@ -54,8 +55,6 @@ constexpr int kRec = 6;                    // doubles of a line record
 constexpr int kColBlock = 1024;            // one size for every column: the reduction order must not depend on the pass
 constexpr int kColPerThread = VAMP_PRED_MAX_SAMPLES / kColBlock;
 constexpr int kTotBlock = 64;
-constexpr long long kDefaultScratch = 256ll << 20;
-constexpr double SQRT_LN2 = 0.83255461115769775635;
 constexpr double HALF_LN_2PI = 0.91893853320467274178;
 constexpr double kHighPwaic = 0.4;         // Vehtari, Gelman & Gabry (2017)
 
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(kEvalBlock) void k_pred_eval(const Item* __restrict
     double* dtab = rec + K * kRec;
     const int s_end = min(task.y + kSamplesPerBlock, I.S);
     const bool voigt = I.q == 4, free_sd = I.noise == nullptr;
-    const unsigned long long gmask = (lanes == 64 ? ~0ull : ((1ull << lanes) - 1ull)) << (sub * lanes);
+    const unsigned long long gmask = vamp::group_mask(lanes, sub);
 
     for (int sb = task.y + wave * nsub; sb < s_end; sb += kEvalWaves * nsub) {      // (uniform per wavefront)
         const int s = sb + sub;
@@ -128,27 +127,7 @@ __global__ __launch_bounds__(kEvalBlock) void k_pred_eval(const Item* __restrict
                 sd = th[I.D - 1];
                 bad_lane = !isfinite(sd) || sd <= 0.0;
             }
-            if (gl < K) {
-                th += I.q * gl;
-                const double a = th[0], c = th[1];
-                double* r = rec + gl * kRec;
-                r[0] = c;
-                if (voigt) {
-                    const double Lw = th[2], G = th[3];
-                    bad_lane = bad_lane || !(isfinite(a) && isfinite(c) && isfinite(Lw) && isfinite(G)) || G <= 0.0 || Lw < 0.0;
-                    const double rG = vamp::rcp_nr(G);
-                    const double y = (Lw * SQRT_LN2) * rG;
-                    r[1] = (2.0 * SQRT_LN2) * rG;
-                    r[2] = y;
-                    r[3] = a * y;                      // tau_k = A y sqrt(pi) H: the evaluator returns sqrt(pi) H
-                    r[4] = vamp::core_pole_factor(y);
-                    r[5] = vamp::core_hy(y);
-                } else {
-                    const double sg = th[2];
-                    bad_lane = bad_lane || !(isfinite(a) && isfinite(c) && isfinite(sg)) || sg <= 0.0;
-                    r[1] = 1.0 / sg; r[2] = 0.0; r[3] = a; r[4] = 0.0; r[5] = 0.0;
-                }
-            }
+            if (gl < K) bad_lane |= vamp::line_record(voigt, th + I.q * gl, rec + gl * kRec);
         }
         const bool bad = (__ballot(bad_lane) & gmask) != 0ull;
         const bool good = valid && !bad;
@@ -255,7 +234,6 @@ __global__ __launch_bounds__(kTotBlock) void k_pred_totals(const Totals* __restr
 }
 
 struct Pass {
-    size_t item0, item1;           // its items (and column sets)
     size_t etask0, etask1;         // its k_pred_eval workgroups
     size_t ctask0, ctask1;         // its k_pred_column workgroups
     int region_doubles = 0;        // LDS of a wavefront of k_pred_eval
@@ -278,47 +256,26 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
     if (n_groups <= 0) return fail(fn + "n_groups must be positive");
     if (!x || !flux || !noise || !n_pix || !n_comp || !mode || !sample_sd || !base || !ld || !n_keep || !walkers)
         return fail(fn + "NULL argument");
-    if (scratch_bytes < 0) return fail(fn + "scratch_bytes must not be negative");
-    std::vector<int> Sg(n_groups), Dg(n_groups);
-    long long tot_pix = 0, tot_noise = 0, tot_s = 0;
-    int s_max = 0;
+    ChainGroups cg;
+    const std::string err = check_chain_groups(fn, n_groups, x, n_pix, n_comp, mode, sample_sd, base, ld, n_keep, walkers, scratch_bytes,
+                                               VAMP_PRED_MAX_SAMPLES, VAMP_PRED_MAX_COMPONENTS,
+                                               "subsample in time: ld * step, ceil(n_keep / step)", cg);
+    if (!err.empty()) return fail(err);
+    const long long tot_pix = cg.tot_pix, tot_s = cg.tot_s;
+    long long tot_noise = 0;
     for (int g = 0; g < n_groups; ++g) {
         const std::string at = fn + "group " + std::to_string(g) + ": ";
-        if (!base[g]) return fail(at + "NULL base pointer");
-        if (!x[g]) return fail(at + "NULL abscissa");
         if (!flux[g]) return fail(at + "NULL flux");
-        if (n_pix[g] <= 0) return fail(at + "n_pix must be positive");
-        if (n_comp[g] < 1 || n_comp[g] > VAMP_PRED_MAX_COMPONENTS)
-            return fail(at + "n_comp = " + std::to_string(n_comp[g]) + " is outside 1 .. " + std::to_string(VAMP_PRED_MAX_COMPONENTS));
-        if (mode[g] == 2) return fail(at + "mode 2 (NBZ3) is not supported: pass the chain in the GAUSS3 (0) or VOIGT4 (1) layout");
-        if (mode[g] != 0 && mode[g] != 1) return fail(at + "mode must be 0 (GAUSS3) or 1 (VOIGT4)");
-        if (sample_sd[g] != 0 && sample_sd[g] != 1) return fail(at + "sample_sd must be 0 or 1");
         if (sample_sd[g] && noise[g]) return fail(at + "noise must be NULL when sample_sd is set: the chain's sd is the noise");
         if (!sample_sd[g] && !noise[g]) return fail(at + "NULL noise without sample_sd");
-        if (n_keep[g] <= 0 || walkers[g] <= 0) return fail(at + "n_keep and walkers must be positive");
-        const long long S = (long long)n_keep[g] * walkers[g];
-        if (S > VAMP_PRED_MAX_SAMPLES)
-            return fail(at + "n_keep * walkers = " + std::to_string(S) + " exceeds " + std::to_string(VAMP_PRED_MAX_SAMPLES) +
-                        " (subsample in time: ld * step, ceil(n_keep / step))");
-        Dg[g] = (mode[g] == 1 ? 4 : 3) * n_comp[g] + sample_sd[g];
-        if (ld[g] < (int64_t)walkers[g] * Dg[g]) return fail(at + "ld < walkers * ndim");
         for (int p = 0; p < n_pix[g]; ++p) {
-            if (!std::isfinite(x[g][p])) return fail(at + "the abscissa is not finite at pixel " + std::to_string(p));
             if (!std::isfinite(flux[g][p])) return fail(at + "the flux is not finite at pixel " + std::to_string(p));
             if (noise[g] && !(std::isfinite(noise[g][p]) && noise[g][p] > 0.0))
                 return fail(at + "the noise is not finite and positive at pixel " + std::to_string(p));
         }
-        Sg[g] = (int)S;
-        s_max = Sg[g] > s_max ? Sg[g] : s_max;
-        tot_pix += n_pix[g];
         tot_noise += noise[g] ? n_pix[g] : 0;
-        tot_s += S;
     }
     if (tot_pix > (1LL << 30)) return fail(fn + "too many outputs");
-    const long long cap = (scratch_bytes ? scratch_bytes : kDefaultScratch) / (long long)sizeof(double);
-    if (cap < s_max)
-        return fail(fn + "scratch_bytes = " + std::to_string(scratch_bytes) + " is less than one column of the largest group (" +
-                    std::to_string((long long)s_max * (long long)sizeof(double)) + " bytes)");
 
     DeviceRestore restore;
     if (set_device(fn, device, restore)) return -1;
@@ -329,7 +286,7 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
     DevBuf staging;
     if (!is_device) {
         std::vector<long long> len(n_groups);
-        for (int g = 0; g < n_groups; ++g) len[g] = chain_span(n_keep[g], ld[g], walkers[g], Dg[g]);
+        for (int g = 0; g < n_groups; ++g) len[g] = chain_span(n_keep[g], ld[g], walkers[g], cg.D[g]);
         if (stage_chains(len, base, st, staging, dbase)) return -1;
     }
 
@@ -359,78 +316,57 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
     HIP_TRY(hipMemcpyAsync(d_main.p, h_in.data(), h_in.size() * sizeof(double), hipMemcpyHostToDevice, st));
     double* dm = d_main.as<double>();
 
-    // the plan: items packed greedily into passes; a group that does not fit what is left of a pass is split over
-    // pixel ranges
+    // the plan (chain_groups.hpp): one item and one column set per range, a group's totals after its last range
+    const PassPlan plan = plan_passes(cg.cap, cg.S, n_pix, n_groups);
+    const long long scratch_len = plan.scratch_len;
+    HIP_TRY(hipMalloc(&d_scratch.p, (size_t)scratch_len * sizeof(double)));
     std::vector<Item> items;
     std::vector<ColSet> sets;
     std::vector<Totals> totals;
     std::vector<int2> etasks, ctasks;
-    std::vector<Pass> passes;
-    std::vector<long long> item_scratch;                 // offset into the pass's scratch
-    long long scratch_len = 0;
-    {
-        Pass cur{};
-        long long used = 0, pix_off = 0, noise_off = 0, s_off = 0;
-        auto close = [&]() {
-            cur.item1 = items.size(); cur.etask1 = etasks.size(); cur.ctask1 = ctasks.size();
-            if (cur.item1 > cur.item0) passes.push_back(cur);
-            scratch_len = used > scratch_len ? used : scratch_len;
-            cur = Pass{};
-            cur.item0 = items.size(); cur.etask0 = etasks.size(); cur.ctask0 = ctasks.size();
-            used = 0;
-        };
-        for (int g = 0; g < n_groups; ++g) {
-            const int S = Sg[g], K = n_comp[g], P = n_pix[g];
-            const int lanes = vamp::group_lanes(VAMP_PRED_NARROW, P, K);
-            const int region = (64 / lanes) * slot_doubles(K);
-            uint8_t* bad = d_bad.as<uint8_t>() + s_off;
-            for (int p0 = 0; p0 < P;) {
-                const long long fit = (cap - used) / S;
-                if (fit == 0) { close(); continue; }              // (an empty pass holds at least one column: cap >= s_max)
-                const int np = (int)((long long)(P - p0) < fit ? (P - p0) : fit);
-                Item it;
-                it.chain = dbase[g];
-                it.x = dm + o_x + pix_off + p0;
-                it.y = dm + o_y + pix_off + p0;
-                it.noise = noise[g] ? dm + o_n + noise_off + p0 : nullptr;
-                it.ln_noise = noise[g] ? dm + o_ln + noise_off + p0 : nullptr;
-                it.ll = nullptr;                                   // (the scratch is allocated when its size is known)
-                it.bad = bad;
-                it.ld = ld[g];
-                it.fs_s = VAMP_PRED_PIXEL_MAJOR ? 1 : np;
-                it.fs_p = VAMP_PRED_PIXEL_MAJOR ? S : 1;
-                it.W = walkers[g]; it.D = Dg[g]; it.K = K; it.q = mode[g] == 1 ? 4 : 3;
-                it.S = S; it.np = np; it.lanes = lanes;
-                ColSet cs;
-                cs.src = nullptr; cs.bad = bad;
-                cs.lppd = dm + o_lppd + pix_off + p0;
-                cs.ll_mean = dm + o_lm + pix_off + p0;
-                cs.pwaic = dm + o_pw + pix_off + p0;
-                cs.counts = p0 == 0 ? d_counts.as<int32_t>() + 2 * g : nullptr;
-                cs.stride_c = it.fs_p; cs.stride_s = it.fs_s; cs.S = S;
-                item_scratch.push_back(used);
-                const int ii = (int)items.size();
-                items.push_back(it);
-                sets.push_back(cs);
-                for (int s0 = 0; s0 < S; s0 += kSamplesPerBlock) etasks.push_back(make_int2(ii, s0));
-                for (int c = 0; c < np; ++c) ctasks.push_back(make_int2(ii, c));
-                cur.region_doubles = region > cur.region_doubles ? region : cur.region_doubles;
-                used += (long long)np * S;
-                p0 += np;
-            }
+    std::vector<Pass> passes(plan.first.size());
+    long long pix_off = 0, noise_off = 0, s_off = 0;     // of the range's group
+    for (const Range& r : plan.ranges) {
+        const int g = r.group, S = cg.S[g], K = n_comp[g], P = n_pix[g], p0 = r.p0, np = r.np;
+        const int lanes = vamp::group_lanes(VAMP_PRED_NARROW, P, K);
+        const int region = (64 / lanes) * slot_doubles(K);
+        Pass& ps = passes[r.pass];
+        if (r.offset == 0) { ps.etask0 = etasks.size(); ps.ctask0 = ctasks.size(); }
+        Item it;
+        it.chain = dbase[g];
+        it.x = dm + o_x + pix_off + p0;
+        it.y = dm + o_y + pix_off + p0;
+        it.noise = noise[g] ? dm + o_n + noise_off + p0 : nullptr;
+        it.ln_noise = noise[g] ? dm + o_ln + noise_off + p0 : nullptr;
+        it.ll = d_scratch.as<double>() + r.offset;
+        it.bad = d_bad.as<uint8_t>() + s_off;
+        it.ld = ld[g];
+        it.fs_s = VAMP_PRED_PIXEL_MAJOR ? 1 : np;
+        it.fs_p = VAMP_PRED_PIXEL_MAJOR ? S : 1;
+        it.W = walkers[g]; it.D = cg.D[g]; it.K = K; it.q = mode[g] == 1 ? 4 : 3;
+        it.S = S; it.np = np; it.lanes = lanes;
+        ColSet cs;
+        cs.src = it.ll; cs.bad = it.bad;
+        cs.lppd = dm + o_lppd + pix_off + p0;
+        cs.ll_mean = dm + o_lm + pix_off + p0;
+        cs.pwaic = dm + o_pw + pix_off + p0;
+        cs.counts = p0 == 0 ? d_counts.as<int32_t>() + 2 * g : nullptr;
+        cs.stride_c = it.fs_p; cs.stride_s = it.fs_s; cs.S = S;
+        const int ii = (int)items.size();
+        items.push_back(it);
+        sets.push_back(cs);
+        for (int s0 = 0; s0 < S; s0 += kSamplesPerBlock) etasks.push_back(make_int2(ii, s0));
+        for (int c = 0; c < np; ++c) ctasks.push_back(make_int2(ii, c));
+        ps.region_doubles = region > ps.region_doubles ? region : ps.region_doubles;
+        ps.etask1 = etasks.size(); ps.ctask1 = ctasks.size();
+        if (p0 + np == P) {
             Totals t;
             t.lppd = dm + o_lppd + pix_off; t.ll_mean = dm + o_lm + pix_off; t.pwaic = dm + o_pw + pix_off; t.P = P;
             totals.push_back(t);
             pix_off += P; noise_off += noise[g] ? P : 0; s_off += S;
         }
-        close();
     }
     if (etasks.size() > 0x7fffffff || ctasks.size() > 0x7fffffff) return fail(fn + "too many workgroups");
-    HIP_TRY(hipMalloc(&d_scratch.p, (size_t)scratch_len * sizeof(double)));
-    for (size_t i = 0; i < items.size(); ++i) {
-        items[i].ll = d_scratch.as<double>() + item_scratch[i];
-        sets[i].src = items[i].ll;
-    }
 
     DevBuf d_items, d_sets, d_totals, d_etasks, d_ctasks;
     if (upload(d_items, items, st) || upload(d_sets, sets, st) || upload(d_totals, totals, st) || upload(d_etasks, etasks, st) ||
@@ -456,12 +392,5 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
         fetch(elpd_se, dm + o_grp + G, G * sz, st) || fetch(p_waic, dm + o_grp + 2 * G, G * sz, st) ||
         fetch(lnl_mean, dm + o_grp + 3 * G, G * sz, st) || fetch(n_high, d_high, G * (long long)sizeof(int32_t), st))
         return -1;
-    std::vector<int32_t> counts((size_t)n_groups * 2);
-    HIP_TRY(hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int g = 0; g < n_groups; ++g) {
-        if (n_used) n_used[g] = counts[2 * g];
-        if (n_bad) n_bad[g] = counts[2 * g + 1];
-    }
-    return 0;
+    return fetch_counts(d_counts, n_groups, n_used, n_bad, st);
 }

@@ -1,6 +1,6 @@
-// side_call.hpp -- the frame of an entry point of a side library (chain_diag.hip, posterior.hip, evidence.hip):
-// the error slot, buffers and the caller's device released on every exit path, device selection, the dynamic-LDS
-// limit, staging of host chains, result copies.  DESIGN.md "The call frame of the side libraries".
+// side_call.hpp -- the frame of an entry point of a side library (chain_diag.hip, posterior.hip, evidence.hip,
+// predictive.hip): the error slot, buffers and the caller's device released on every exit path, device selection, the
+// dynamic-LDS limit, staging of host chains, result copies.  DESIGN.md "The call frame of the side libraries".
 //
 // Host code only.  Each library is one translation unit built with -fvisibility=hidden, so each holds its own copy
 // of the state below (the error slot, the record of raised limits).  The argument checks, their messages and
@@ -121,6 +121,19 @@ inline int stage_chains(const std::vector<long long>& len, const double* const* 
 inline int fetch(void* dst, const void* src, long long bytes, hipStream_t st) {
     if (!dst || bytes == 0) return 0;
     HIP_TRY(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// the end of a call: the device's {n_used, n_bad} pair of every group back, the stream drained (the fetches queued
+// before are then done too), the pairs fanned into the caller's arrays (either may be NULL)
+inline int fetch_counts(const DevBuf& d_counts, int n_groups, int32_t* n_used, int32_t* n_bad, hipStream_t st) {
+    std::vector<int32_t> counts((size_t)n_groups * 2);
+    HIP_TRY(hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int g = 0; g < n_groups; ++g) {
+        if (n_used) n_used[g] = counts[2 * g];
+        if (n_bad) n_bad[g] = counts[2 * g + 1];
+    }
     return 0;
 }
 

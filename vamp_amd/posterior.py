@@ -17,9 +17,9 @@ import ctypes as C
 import numpy as np
 
 from . import _post_lib
-from ._sidelib import Q_OF_MODE, fits_with_chain, region_bases
+from ._sidelib import (MAX_CHAIN_SAMPLES as MAX_SAMPLES, chain_args, check_chain_shapes, context_layout, fits_with_chain, host_layout,
+                       per_group, time_step)
 
-MAX_SAMPLES = 16384           # VAMP_POST_MAX_SAMPLES of include/vamp_post.h
 MAX_PROBS = 16
 DEFAULT_PROBS = (0.025, 0.16, 0.5, 0.84, 0.975)
 
@@ -64,16 +64,12 @@ def _call(device, xs, n_comp, modes, sample_sd, bases, is_device, ld, n_keep, wa
            "comp_ew_mean": np.empty(tk), "comp_ew_sd": np.empty(tk), "comp_ew_q": np.empty((tk, Q)),
            "n_used": np.empty(G, dtype=np.int32), "n_bad": np.empty(G, dtype=np.int32)}
     xp = (C.c_void_p * G)(*[x.ctypes.data for x in xs])
-    bp = (C.c_void_p * G)(*[int(b) for b in bases])
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    n_pix, n_comp, modes, sample_sd, n_keep, walkers = (i32(a) for a in ([x.size for x in xs], n_comp, modes, sample_sd, n_keep, walkers))
-    ld = np.ascontiguousarray(ld, dtype=np.int64)
     widths = np.ascontiguousarray(widths, dtype=np.float64)
     ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
     _post_lib.check(lib.vamp_post_summaries(
-        int(device), C.c_void_p(stream or 0), G, xp, n_pix.ctypes.data_as(ip), n_comp.ctypes.data_as(ip), modes.ctypes.data_as(ip),
-        sample_sd.ctypes.data_as(ip), bp, int(bool(is_device)), ld.ctypes.data_as(C.POINTER(C.c_int64)), n_keep.ctypes.data_as(ip),
-        walkers.ctypes.data_as(ip), widths.ctypes.data_as(dp), Q, probs.ctypes.data_as(dp), int(scratch_bytes),
+        int(device), C.c_void_p(stream or 0), G, xp,
+        *chain_args([x.size for x in xs], n_comp, modes, sample_sd, bases, is_device, ld, n_keep, walkers),
+        widths.ctypes.data_as(dp), Q, probs.ctypes.data_as(dp), int(scratch_bytes),
         *[out[k].ctypes.data_as(dp) for k in _FLAT[:9]], out["n_used"].ctypes.data_as(ip), out["n_bad"].ctypes.data_as(ip)), lib)
     return out
 
@@ -81,9 +77,8 @@ def _call(device, xs, n_comp, modes, sample_sd, bases, is_device, ld, n_keep, wa
 def _post_host(xs, arrays, n_comp, modes, sample_sd, widths, probs, steps, device, scratch_bytes):
     """the library call for contiguous fp64 [N, W, D] host arrays, every ``steps[g]``-th time read in place (tests
     put the numpy restatement here)"""
-    return _call(device, xs, n_comp, modes, sample_sd, [a.ctypes.data for a in arrays], False,
-                 [a.shape[1] * a.shape[2] * s for a, s in zip(arrays, steps)], [-(-a.shape[0] // s) for a, s in zip(arrays, steps)],
-                 [a.shape[1] for a in arrays], widths, probs, scratch_bytes)
+    bases, ld, n_keep, walkers = host_layout(arrays, steps)
+    return _call(device, xs, n_comp, modes, sample_sd, bases, False, ld, n_keep, walkers, widths, probs, scratch_bytes)
 
 
 def _split(flat, n_pix, n_comp, probs, steps):
@@ -101,22 +96,6 @@ def _split(flat, n_pix, n_comp, probs, steps):
     return out
 
 
-def _per_group(v, G, cast):
-    return [cast(v)] * G if np.isscalar(v) else [cast(e) for e in v]
-
-
-def time_step(n_keep, walkers):
-    """the smallest step s for which every s-th of ``n_keep`` kept samples of ``walkers`` walkers fits the library:
-    ceil(n_keep / s) * walkers <= MAX_SAMPLES"""
-    if walkers > MAX_SAMPLES:
-        raise ValueError(f"an ensemble of {walkers} walkers exceeds the {MAX_SAMPLES} samples the library takes")
-    rows = MAX_SAMPLES // walkers
-    step = max(1, -(-n_keep // rows))
-    while -(-n_keep // step) > rows:
-        step += 1
-    return step
-
-
 def posterior_summaries(xs, chains, n_comp, mode, sample_sd=False, probs=DEFAULT_PROBS, pixel_width=1.0, device=0,
                         scratch_bytes=0, steps=1):
     """Summaries of one host [N, W, D] chain on the abscissa ``xs`` (returns one ``PosteriorSummary``) or of a list
@@ -128,17 +107,12 @@ def posterior_summaries(xs, chains, n_comp, mode, sample_sd=False, probs=DEFAULT
     xs = [np.ascontiguousarray(x, dtype=np.float64) for x in ([xs] if single else xs)]
     if len(xs) != len(arrays):
         raise ValueError("one abscissa per chain is required")
-    for a in arrays:
-        if a.ndim != 3:
-            raise ValueError("every chain must be an [N, W, D] array")
     G = len(arrays)
     if G == 0:
         return []
-    n_comp, modes, sds = _per_group(n_comp, G, int), _per_group(mode, G, int), _per_group(sample_sd, G, lambda v: int(bool(v)))
-    widths, steps = _per_group(pixel_width, G, float), _per_group(steps, G, int)
-    for a, k, m, sd in zip(arrays, n_comp, modes, sds):
-        if m in Q_OF_MODE and a.shape[2] != Q_OF_MODE[m] * k + sd:
-            raise ValueError(f"a chain of {a.shape[2]} parameters does not hold {k} lines of mode {m} (sample_sd = {sd})")
+    n_comp, modes, sds = per_group(n_comp, G, int), per_group(mode, G, int), per_group(sample_sd, G, lambda v: int(bool(v)))
+    widths, steps = per_group(pixel_width, G, float), per_group(steps, G, int)
+    check_chain_shapes(arrays, n_comp, modes, sds, [f"sample_sd = {sd}" for sd in sds])
     probs = _probs(probs)
     flat = _post_host(xs, arrays, n_comp, modes, sds, widths, probs, steps, int(device), int(scratch_bytes))
     res = _split(flat, [x.size for x in xs], n_comp, probs, steps)
@@ -153,15 +127,12 @@ def context_posterior(ctx, chain_ptr, n_keep, xs, probs=DEFAULT_PROBS, pixel_wid
     ctx.synchronize()                  # the sampler's stream is done with the chain before the default stream reads it
     if isinstance(xs, np.ndarray) and xs.ndim == 1:
         xs = [xs]
-    W, ndims, R = int(ctx.W), list(ctx.ndims), len(ctx.ndims)
+    R = len(ctx.ndims)
     if len(xs) != R:
         raise ValueError("one abscissa per region of the context is required")
-    mode = int(ctx.mode)
-    ks = [int(k) for k in ctx.n_comp]
-    sds = [d - Q_OF_MODE.get(mode, 3) * k for d, k in zip(ndims, ks)]
+    ks, modes, sds, bases, ld, n_keep, walkers = context_layout(ctx, chain_ptr, n_keep)
     probs = _probs(probs)
-    flat = _call(ctx.device, xs, ks, [mode] * R, sds, region_bases(ctx, chain_ptr), True, [ctx.total_theta] * R, [int(n_keep)] * R, [W] * R,
-                 _per_group(pixel_width, R, float), probs, scratch_bytes)
+    flat = _call(ctx.device, xs, ks, modes, sds, bases, True, ld, n_keep, walkers, per_group(pixel_width, R, float), probs, scratch_bytes)
     return _split(flat, [len(x) for x in xs], ks, probs, [1] * R)
 
 

@@ -18,10 +18,9 @@ import ctypes as C
 import numpy as np
 
 from . import _pred_lib
-from ._sidelib import Q_OF_MODE, fits_with_chain, region_bases
-from .posterior import _per_group, time_step
+from ._sidelib import (MAX_CHAIN_SAMPLES as MAX_SAMPLES, chain_args, check_chain_shapes, context_layout, fits_with_chain, host_layout,
+                       per_group, time_step)
 
-MAX_SAMPLES = 16384           # VAMP_PRED_MAX_SAMPLES of include/vamp_pred.h: posterior.time_step serves both libraries
 HIGH_P_WAIC = 0.4             # a pixel's WAIC is not to be trusted past this p_waic (Vehtari, Gelman & Gabry 2017)
 
 _PIX = ("lppd", "ll_mean", "p_waic_pix")
@@ -78,16 +77,11 @@ def _call(device, xs, fluxes, noises, n_comp, modes, sample_sd, bases, is_device
     out.update({k: np.empty(G) for k in _GRP if k in want})
     out.update({k: np.empty(G, dtype=np.int32) for k in _CNT if k in want})
     ptrs = lambda arrays: (C.c_void_p * G)(*[None if a is None else a.ctypes.data for a in arrays])
-    bp = (C.c_void_p * G)(*[int(b) for b in bases])
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    n_pix, n_comp, modes, sample_sd, n_keep, walkers = (i32(a) for a in ([x.size for x in xs], n_comp, modes, sample_sd, n_keep, walkers))
-    ld = np.ascontiguousarray(ld, dtype=np.int64)
     ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
     arg = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else None
     _pred_lib.check(lib.vamp_pred_pointwise(
-        int(device), C.c_void_p(stream or 0), G, ptrs(xs), ptrs(fluxes), ptrs(noises), n_pix.ctypes.data_as(ip), n_comp.ctypes.data_as(ip),
-        modes.ctypes.data_as(ip), sample_sd.ctypes.data_as(ip), bp, int(bool(is_device)), ld.ctypes.data_as(C.POINTER(C.c_int64)),
-        n_keep.ctypes.data_as(ip), walkers.ctypes.data_as(ip), int(scratch_bytes),
+        int(device), C.c_void_p(stream or 0), G, ptrs(xs), ptrs(fluxes), ptrs(noises),
+        *chain_args([x.size for x in xs], n_comp, modes, sample_sd, bases, is_device, ld, n_keep, walkers), int(scratch_bytes),
         *[arg(k, dp) for k in _PIX + _GRP], *[arg(k, ip) for k in _CNT]), lib)
     return out
 
@@ -95,9 +89,8 @@ def _call(device, xs, fluxes, noises, n_comp, modes, sample_sd, bases, is_device
 def _pred_host(xs, fluxes, noises, arrays, n_comp, modes, steps, device, scratch_bytes):
     """the library call for contiguous fp64 [N, W, D] host arrays, every ``steps[g]``-th time read in place (tests
     put the numpy restatement here)"""
-    return _call(device, xs, fluxes, noises, n_comp, modes, [int(n is None) for n in noises], [a.ctypes.data for a in arrays], False,
-                 [a.shape[1] * a.shape[2] * s for a, s in zip(arrays, steps)], [-(-a.shape[0] // s) for a, s in zip(arrays, steps)],
-                 [a.shape[1] for a in arrays], scratch_bytes)
+    bases, ld, n_keep, walkers = host_layout(arrays, steps)
+    return _call(device, xs, fluxes, noises, n_comp, modes, [int(n is None) for n in noises], bases, False, ld, n_keep, walkers, scratch_bytes)
 
 
 def _split(flat, n_pix, steps):
@@ -120,16 +113,11 @@ def pointwise_predictive(xs, fluxes, noises, chains, n_comp, mode, device=0, scr
     xs, fluxes, noises = ([v] if single else list(v) for v in (xs, fluxes, noises))
     if not len(xs) == len(fluxes) == len(noises) == len(arrays):
         raise ValueError("one abscissa, one flux and one noise (or None) per chain are required")
-    for a in arrays:
-        if a.ndim != 3:
-            raise ValueError("every chain must be an [N, W, D] array")
     G = len(arrays)
     if G == 0:
         return []
-    n_comp, modes, steps = _per_group(n_comp, G, int), _per_group(mode, G, int), _per_group(steps, G, int)
-    for a, k, m, n in zip(arrays, n_comp, modes, noises):
-        if m in Q_OF_MODE and a.shape[2] != Q_OF_MODE[m] * k + int(n is None):
-            raise ValueError(f"a chain of {a.shape[2]} parameters does not hold {k} lines of mode {m} (free sd = {n is None})")
+    n_comp, modes, steps = per_group(n_comp, G, int), per_group(mode, G, int), per_group(steps, G, int)
+    check_chain_shapes(arrays, n_comp, modes, [int(n is None) for n in noises], [f"free sd = {n is None}" for n in noises])
     flat = _pred_host(xs, fluxes, noises, arrays, n_comp, modes, steps, int(device), int(scratch_bytes))
     res = _split(flat, [len(x) for x in xs], steps)
     return res[0] if single else res
@@ -143,17 +131,14 @@ def context_predictive(ctx, chain_ptr, n_keep, xs, fluxes, noises, scratch_bytes
     ctx.synchronize()                  # the sampler's stream is done with the chain before the default stream reads it
     if isinstance(xs, np.ndarray) and xs.ndim == 1:
         xs, fluxes, noises = [xs], [fluxes], [noises]
-    W, ndims, R = int(ctx.W), list(ctx.ndims), len(ctx.ndims)
+    R = len(ctx.ndims)
     if not len(xs) == len(fluxes) == len(noises) == R:
         raise ValueError("one abscissa, one flux and one noise (or None) per region of the context are required")
-    mode = int(ctx.mode)
-    ks = [int(k) for k in ctx.n_comp]
-    sds = [d - Q_OF_MODE.get(mode, 3) * k for d, k in zip(ndims, ks)]
+    ks, modes, sds, bases, ld, n_keep, walkers = context_layout(ctx, chain_ptr, n_keep)
     for sd, n in zip(sds, noises):
         if bool(sd) != (n is None):
             raise ValueError("a region's noise is None exactly when the context samples its sd")
-    flat = _call(ctx.device, xs, fluxes, noises, ks, [mode] * R, sds, region_bases(ctx, chain_ptr), True, [ctx.total_theta] * R,
-                 [int(n_keep)] * R, [W] * R, scratch_bytes)
+    flat = _call(ctx.device, xs, fluxes, noises, ks, modes, sds, bases, True, ld, n_keep, walkers, scratch_bytes)
     return _split(flat, [len(x) for x in xs], [1] * R)
 
 
