@@ -11,7 +11,8 @@ Spectra are independent: no communication.  New flags: --walkers, --iterations, 
 (per-pixel arithmetic; $VAMP_DTYPE overrides the default), --backend hip ($VAMP_BACKEND), --posterior (also write
 ``<prefix>posterior.h5``: the posterior flux band and equivalent widths with credible intervals, vamp_amd.posterior),
 --evidence (also write ``<prefix>evidence.h5``: ln Z of every kept fit's model, vamp_amd.evidence), --predictive (also
-write ``<prefix>predictive.h5``: the pointwise log predictive density and WAIC of every kept fit, vamp_amd.predictive).
+write ``<prefix>predictive.h5``: the pointwise log predictive density and WAIC of every kept fit, vamp_amd.predictive),
+--loo (also write ``<prefix>loo.h5``: PSIS-LOO and the Pareto shape khat of every pixel of every kept fit, vamp_amd.loo).
 """
 import argparse
 import glob
@@ -102,6 +103,12 @@ def fit_one(path, args, device=0):
         if args.output_folder is not None and getattr(spec, "output_filename", None):
             spec.write_predictive(pred)
         rec["predictive_seconds"] = time.perf_counter() - t1
+    if getattr(args, "loo", False):
+        t1 = time.perf_counter()
+        loo = spec.loo()
+        if args.output_folder is not None and getattr(spec, "output_filename", None):
+            spec.write_loo(loo)
+        rec["loo_seconds"] = time.perf_counter() - t1
     print("vamp_perf " + json.dumps(rec), flush=True)
     if args.output_folder is not None and getattr(spec, "output_filename", None):
         with open(spec.output_filename + "perf.json", "w") as fh:
@@ -150,6 +157,9 @@ def main(argv=None, _fit_name="vamp_amd.do_vamp:fit_one"):
     p.add_argument("--predictive", action="store_true",
                    help="also compute the pointwise log predictive density and WAIC of every kept fit from its chain on the "
                         "GPU, written to <prefix>predictive.h5 (off by default)")
+    p.add_argument("--loo", action="store_true",
+                   help="also compute the Pareto-smoothed leave-one-out predictive density (PSIS-LOO) and the Pareto shape khat "
+                        "of every pixel of every kept fit from its chain on the GPU, written to <prefix>loo.h5 (off by default)")
     args = p.parse_args(argv)
     if args.backend != "hip":            # (argparse does not check a default taken from the environment)
         sys.exit("do_vamp: backend %r is not available: the product runs on libvamp_hip.so only (no CPU fallback)" % args.backend)

@@ -83,6 +83,7 @@ class _EnsembleMCMC:
         self._diag = None          # ChainDiagnostics of the device-unit chain, computed once
         self._post = {}            # probs -> PosteriorSummary of the device-unit chain at unit pixel width
         self._pred = None          # PredictiveRecord of the device-unit chain, computed once
+        self._loo = None           # LooRecord of the device-unit chain, computed once
 
     def sample(self, iter, burn=0, thin=1, progress_bar=False, **_ignored):
         self._fit._run_sampler(int(iter), int(burn), int(thin))
@@ -195,6 +196,23 @@ class _EnsembleMCMC:
 
     def _set_predictive(self, record):
         self._pred = record
+
+    def loo(self):
+        """The fit's ``LooRecord`` (vamp_amd.loo): the Pareto-smoothed leave-one-out predictive density of every pixel
+        under the kept samples of the whole ensemble, its Pareto shape ``khat``, ``elpd_loo`` with its standard error,
+        ``p_loo`` and ``looic`` = -2 elpd_loo, in the fit's pixel order.  One GPU call, cached per fit."""
+        if self._loo is None:
+            fit = self._fit
+            if fit._chain_dev is None:
+                raise RuntimeError("no chain: run the sampler first")
+            from . import loo
+            _, recs = loo.fits_loo([fit], device=fit.device)
+            if self._loo is None:              # (fits_loo fills the cache)
+                self._set_loo(recs[0])
+        return self._loo
+
+    def _set_loo(self, record):
+        self._loo = record
 
 
 class _Stats(Mapping):
@@ -515,6 +533,7 @@ class VPfit():
         mc_._thin, mc_._diag = max(1, int(thin)), None
         mc_._post = {}
         mc_._pred = None
+        mc_._loo = None
         if self._voigt:      # the reference's callers ask for est_sigma_k in Voigt mode too (vpspectrum.py:400)
             for k in range(self._n):
                 mc_._derived["est_sigma_%d" % k] = ("est_G_%d" % k, self.GaussianWidth)

@@ -59,13 +59,16 @@ class VPregion():
         three repeats keeps falling; stop early once the mean reduced chi^2 is under ``chi_limit``.
         The first rung is judged by the LAST of its three BICs, as in the reference (:63).
         ``criterion='evidence'``: the number of lines is chosen by ln Z instead (``_region_fit_evidence``);
-        ``criterion='waic'``: by the expected log predictive density of the chains (``_region_fit_waic``)."""
+        ``criterion='waic'``: by the expected log predictive density of the chains (``_region_fit_waic``);
+        ``criterion='loo'``: the same ladder scored by PSIS-LOO (``_region_fit_loo``)."""
         if criterion == 'evidence':
             return self._region_fit_evidence(verbose, iterations, thin, burn, evidence_kw or {})
         if criterion == 'waic':
             return self._region_fit_waic(verbose, iterations, thin, burn)
+        if criterion == 'loo':
+            return self._region_fit_loo(verbose, iterations, thin, burn)
         if criterion != 'bic':
-            raise ValueError("criterion must be 'bic', 'evidence' or 'waic'")
+            raise ValueError("criterion must be 'bic', 'evidence' or 'waic' or 'loo'")
         say = print if verbose else (lambda *a, **k: None)
         self._attempt += 1
         say("Setting initial number of lines to: {}".format(self.n))
@@ -160,6 +163,31 @@ class VPregion():
             kept = trial
         self.fit = kept
         self.fit.predictive = self.predictive[self.n]
+
+    def _region_fit_loo(self, verbose, iterations, thin, burn):
+        """The WAIC ladder's rungs (``_waic_fit_n``) scored by ``elpd_loo`` (vamp_amd.loo): add a component while it rises
+        by more than the standard error of the difference, paired pixel by pixel.  The records are kept as
+        ``self.loo[n]``, the kept fit carries its record as ``fit.loo`` and the dropped fit is released."""
+        from . import predictive
+        say = print if verbose else (lambda *a, **k: None)
+        self._attempt += 1
+        say("Setting initial number of lines to: {}".format(self.n))
+        kept = self._waic_fit_n(self.n, iterations, thin, burn)
+        self.loo = {self.n: kept.mcmc.loo()}
+        while self.n < MAX_COMPONENTS:
+            trial = self._waic_fit_n(self.n + 1, iterations, thin, burn)
+            self.loo[self.n + 1] = trial.mcmc.loo()
+            rise, se = predictive.compare(self.loo[self.n], self.loo[self.n + 1])
+            if not rise > se:
+                say("elpd_loo rose by {:.2f} (paired standard error {:.2f}): keeping n={}.".format(rise, se, self.n))
+                self._release(trial)
+                break
+            self.n += 1
+            say("elpd_loo rose by {:.2f} (paired standard error {:.2f}): n={}.".format(rise, se, self.n))
+            self._release(kept)
+            kept = trial
+        self.fit = kept
+        self.fit.loo = self.loo[self.n]
 
     @staticmethod
     def _release(fit):

@@ -510,6 +510,36 @@ class VPspectrum():
         h5min.write(path, {k: np.array(v) for k, v in pred.items()})
         return path
 
+    def loo(self, scratch_bytes=0):
+        """After ``fit_spectrum`` (batched or not): PSIS-LOO of every kept fit from ONE GPU call over their chains
+        (vamp_amd.loo).  A dict: ``elpd_loo_pix`` / ``p_loo_pix`` / ``khat`` / ``lppd`` [n_pixels] in wavelength order
+        (flipped like ``_harvest``; NaN outside regions), and per region ``elpd_loo`` / ``elpd_loo_se`` / ``p_loo`` /
+        ``looic`` / ``n_high_k`` / ``n_used`` / ``n_bad`` / ``n_comp`` / ``time_step`` [n_regions]."""
+        from . import loo
+        npx, regs = len(self.flux_array), self.regions
+        have, recs = loo.fits_loo([r.fit for r in regs], device=getattr(self, "device", 0), scratch_bytes=scratch_bytes)
+        if len(have) != len(regs):
+            raise RuntimeError("loo: %d of %d regions have no chain" % (len(regs) - len(have), len(regs)))
+        pix = ("elpd_loo_pix", "p_loo_pix", "khat", "lppd")
+        out = {k: np.full(npx, np.nan) for k in pix}
+        for k in ("elpd_loo", "elpd_loo_se", "p_loo", "looic"):
+            out[k] = np.array([getattr(r, k) for r in recs], dtype=np.float64)
+        for k in ("n_high_k", "n_used", "n_bad"):
+            out[k] = np.array([getattr(r, k) for r in recs], dtype=np.int32)
+        out["n_comp"] = np.array([r.fit._n for r in regs], dtype=np.int32)
+        out["time_step"] = np.array([r.step for r in recs], dtype=np.int32)
+        for (start, end), r in zip(self.region_pixels, recs):
+            for k in pix:
+                out[k][start:end] = np.flip(getattr(r, k), 0)
+        return out
+
+    def write_loo(self, rec):
+        """``loo()``'s dict as ``<prefix>loo.h5`` through vamp_amd/h5min.py; returns the path"""
+        from . import h5min
+        path = self.output_filename + 'loo.h5'
+        h5min.write(path, {k: np.array(v) for k, v in rec.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
