@@ -23,6 +23,8 @@ ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
 ap.add_argument("--profile", default=None, help="write a cProfile of fit_spectrum (sorted by total time) to this file")
 ap.add_argument("--dump", default=None, help="save per-region n and best reduced chi^2 to this .npz (to compare two runs)")
 ap.add_argument("--quiet", action="store_true")
+ap.add_argument("--relabel", action="store_true",
+                help="also undo label switching in the kept fits' chains (VPspectrum.relabel) and report the diagnostics before and after")
 a = ap.parse_args()
 from vamp_amd.vpspectrum import VPspectrum
 q = np.load(os.path.join(ROOT, "tests", "golden", "q1422_spectrum.npz"))
@@ -61,6 +63,23 @@ from vamp_amd import diagnostics
 t1 = time.perf_counter()
 recs, skipped = diagnostics.fits_diagnostics([r.fit for r in sp.regions])
 out["diagnostics"] = dict(diagnostics.summary(recs), seconds=time.perf_counter() - t1, fits=len(recs), skipped=skipped)
+
+# how much of that is label switching: the same numbers from the relabelled chains (one relabelling call, one diagnostics call)
+if a.relabel:
+    t1 = time.perf_counter()
+    rl = sp.relabel()
+    multi = rl["n_comp"] > 1
+    out["relabel"] = {"seconds": time.perf_counter() - t1, "regions_with_more_than_one_line": int(multi.sum()),
+                      "share_of_samples_switched": float(rl["n_switched"].sum() / max(1, rl["n_used"].sum())),
+                      "share_of_samples_switched_in_multi_line_regions": float(rl["n_switched"][multi].sum() / max(1, rl["n_used"][multi].sum())),
+                      "regions_with_a_switched_sample": int(np.sum(rl["n_switched"] > 0)),
+                      "regions_not_converged": int(np.sum((rl["converged"] == 0) & multi)), "rounds_max": int(rl["n_iter"].max()),
+                      "bad_samples": int(rl["n_bad"].sum()),
+                      "regions_whose_max_r_hat_fell_by_a_tenth": int(np.sum(rl["max_r_hat_after"] < 0.9 * rl["max_r_hat_before"])),
+                      "diagnostics_after": {"min_n_eff": float(np.nanmin(rl["min_n_eff_after"])),
+                                            "frac_regions_n_eff_below_50": float(np.mean(rl["min_n_eff_after"] < 50.0)),
+                                            "max_r_hat": float(np.nanmax(rl["max_r_hat_after"])),
+                                            "frac_regions_unreliable_tau": float(np.mean(rl["tau_reliable_after"] == 0))}}
 
 
 def compare_with_vpm(params):

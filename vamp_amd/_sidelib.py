@@ -1,7 +1,7 @@
 """What the ctypes bindings of the side libraries (``_diag_lib``, ``_post_lib``, ``_evid_lib``, ``_pred_lib``,
-``_loo_lib``) and their callers (``diagnostics``, ``posterior``, ``evidence``, ``predictive``, ``loo``) share; the second
-half is what the callers that walk every sample of a chain (``posterior``, ``predictive``, ``loo``) hand their
-libraries alike.
+``_loo_lib``, ``_relabel_lib``) and their callers (``diagnostics``, ``posterior``, ``evidence``, ``predictive``, ``loo``,
+``relabel``) share; the second half is what the callers that walk every sample of a chain (``posterior``, ``predictive``,
+``loo``, ``relabel``) hand their libraries alike.
 
 The rules of a binding are those of ``_lib``: no fallback (a missing library raises, every call needs a GPU), and
 the library is loaded after torch so that it binds the ROCm runtime torch has mapped -- the one libvamp_hip.so binds

@@ -19,11 +19,11 @@ DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("ff_matrix.inc", "ff_mat
 # (profiles/r03_b_f32_variants.txt; MI355X_MICROARCH.md lists packed fp32 VALU as an anti-lever).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-shared", "-fPIC"]
 
-# The five side libraries share their flags, the frame of their entry points (side_call.hpp) and -- all but the
+# The side libraries share their flags, the frame of their entry points (side_call.hpp) and -- all but the
 # diagnostics -- the lane-group evaluator (lane_group.hpp); the posterior, the predictive density and PSIS-LOO also the
 # chain checks and the pass planner (chain_groups.hpp): an edit of a shared header rebuilds what includes it
 SIDE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
-POST_FLAGS = EVID_FLAGS = PRED_FLAGS = LOO_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
+POST_FLAGS = EVID_FLAGS = PRED_FLAGS = LOO_FLAGS = RELABEL_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
 SIDE_CALL = os.path.join(HERE, "csrc", "side_call.hpp")
 LANE_GROUP = os.path.join(HERE, "csrc", "lane_group.hpp")
 CHAIN_GROUPS = os.path.join(HERE, "csrc", "chain_groups.hpp")
@@ -61,6 +61,12 @@ LOO_SRC = os.path.join(HERE, "csrc", "loo.hip")
 LOO_OUT = os.path.join(HERE, "libvamp_loo.so")
 LOO_DEPS = [LOO_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, os.path.join(HERE, "csrc", "voigt_math.hpp"),
             os.path.join(HERE, "..", "include", "vamp_loo.h")]
+
+# libvamp_relabel.so (include/vamp_relabel.h): the relabelling that undoes label switching, a seventh library on the
+# same terms; it moves parameters and evaluates nothing, so it shares only the call frame
+RELABEL_SRC = os.path.join(HERE, "csrc", "relabel.hip")
+RELABEL_OUT = os.path.join(HERE, "libvamp_relabel.so")
+RELABEL_DEPS = [RELABEL_SRC, SIDE_CALL, os.path.join(HERE, "csrc", "relabel_host.hpp"), os.path.join(HERE, "..", "include", "vamp_relabel.h")]
 
 
 def _compile(out, src, deps, flags, force, verbose):
@@ -102,13 +108,19 @@ def build_loo(force=False, verbose=True, out=None, defines=()):
     return _compile(out or LOO_OUT, LOO_SRC, LOO_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
+def build_relabel(force=False, verbose=True, out=None, defines=()):
+    """libvamp_relabel.so; returns its path.  ``out`` / ``defines``: a variant build beside it"""
+    return _compile(out or RELABEL_OUT, RELABEL_SRC, RELABEL_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
+
+
 def build(force=False, verbose=True):
-    """The six libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
+    """The seven libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
     build_diag(force=force, verbose=verbose)
     build_post(force=force, verbose=verbose)
     build_evid(force=force, verbose=verbose)
     build_pred(force=force, verbose=verbose)
     build_loo(force=force, verbose=verbose)
+    build_relabel(force=force, verbose=verbose)
     return _compile(OUT, SRC, DEPS, FLAGS, force, verbose)
 
 

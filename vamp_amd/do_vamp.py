@@ -113,6 +113,20 @@ def fit_one(path, args, device=0):
     if args.output_folder is not None and getattr(spec, "output_filename", None):
         with open(spec.output_filename + "perf.json", "w") as fh:
             json.dump(rec, fh)
+    if getattr(args, "relabel", False):
+        # After the perf record is out: it is what it is without the option, and a region without a chain must not cost
+        # a finished fit its record.  Its own file and its own line; params.h5 and the harvest are not touched.
+        t1 = time.perf_counter()
+        try:
+            relabelled = spec.relabel()
+        except RuntimeError as err:
+            print("do_vamp: --relabel left out: %s" % err, file=sys.stderr, flush=True)
+        else:
+            if args.output_folder is not None and getattr(spec, "output_filename", None):
+                spec.write_relabel(relabelled)
+            print("vamp_relabel " + json.dumps({"spectrum": rec["spectrum"], "relabel_seconds": time.perf_counter() - t1,
+                                                "regions_not_converged": int((relabelled["converged"] == 0).sum()),
+                                                "samples_switched": int(relabelled["n_switched"].sum())}), flush=True)
     return params
 
 
@@ -160,6 +174,10 @@ def main(argv=None, _fit_name="vamp_amd.do_vamp:fit_one"):
     p.add_argument("--loo", action="store_true",
                    help="also compute the Pareto-smoothed leave-one-out predictive density (PSIS-LOO) and the Pareto shape khat "
                         "of every pixel of every kept fit from its chain on the GPU, written to <prefix>loo.h5 (off by default)")
+    p.add_argument("--relabel", action="store_true",
+                   help="also undo label switching in the chains of the kept fits on the GPU: per region how many samples were "
+                        "switched and the largest R-hat before and after, per line the mean and standard deviation of its "
+                        "label, written to <prefix>relabel.h5 (off by default; params.h5 is not changed)")
     args = p.parse_args(argv)
     if args.backend != "hip":            # (argparse does not check a default taken from the environment)
         sys.exit("do_vamp: backend %r is not available: the product runs on libvamp_hip.so only (no CPU fallback)" % args.backend)

@@ -28,14 +28,34 @@ class Evidence:
     """ln Z of one region: ``lnZ`` (stepping stone), ``lnZ_se`` (from 8 time blocks), ``lnZ_ti`` (trapezoid of the mean
     ln L over beta, a diagnostic), ``betas`` [T], ``mean_lnL`` / ``var_lnL`` / ``move_accept`` [T], ``swap_accept``
     [T - 1], and -- when asked for -- the beta = 1 rung's kept ``chain`` [n_keep, W, D] with its ``chain_lnl``
-    [n_keep, W] (else None).  ``lnl_trace`` / ``swap_trace``: see the header (tests)."""
+    [n_keep, W] (else None).  ``lnl_trace`` / ``swap_trace``: see the header (tests).  ``n_comp`` / ``mode`` /
+    ``sample_sd``: the layout of ``chain``, which ``relabel()`` reads."""
 
     __slots__ = ("lnZ", "lnZ_se", "lnZ_ti", "betas", "mean_lnL", "var_lnL", "move_accept", "swap_accept", "chain", "chain_lnl",
-                 "lnl_trace", "swap_trace")
+                 "lnl_trace", "swap_trace", "n_comp", "mode", "sample_sd", "_relabel")
 
     def __init__(self, **fields):
         for k in self.__slots__:
             setattr(self, k, fields.get(k))
+
+    def relabel(self, max_iter=10, device=0):
+        """The ``RelabelRecord`` (vamp_amd.relabel) of the kept beta = 1 chain, with the relabelled chain in its
+        ``chain``.  The ensemble started from independent prior draws, so every walker carries its own labelling and
+        ``chain`` cannot be summarised per line as it stands.  The reference is the sample of highest ln L.  Cached per
+        ``max_iter``."""
+        if self.chain is None or self.chain_lnl is None or self.n_comp is None:
+            raise RuntimeError("no chain: ask for it with return_chain=True")
+        cache = self._relabel if self._relabel is not None else {}
+        self._relabel = cache
+        if int(max_iter) not in cache:
+            from . import relabel
+            K, q = int(self.n_comp), Q_OF_MODE[int(self.mode)]
+            with np.errstate(invalid="ignore"):
+                t, w = np.unravel_index(np.nanargmax(self.chain_lnl), self.chain_lnl.shape)
+            ref = self.chain[t, w, :K * q].reshape(K, q)
+            cache[int(max_iter)] = relabel.relabel_chains(self.chain, K, int(self.mode), int(bool(self.sample_sd)), ref, max_iter=max_iter,
+                                                          device=device, return_chain=True)
+        return cache[int(max_iter)]
 
     def __repr__(self):
         return f"Evidence(lnZ={self.lnZ!r}, lnZ_se={self.lnZ_se!r}, lnZ_ti={self.lnZ_ti!r}, T={len(self.betas)})"
@@ -145,6 +165,8 @@ def log_evidence(regions, n_temps=16, walkers=32, steps=600, burn=200, swap_ever
         betas = default_betas(n_temps)
     recs = [Evidence(**r) for r in _run(specs, np.asarray(betas, dtype=np.float64), walkers, steps, burn, swap_every, seed, a, start, device,
                                         return_chain, trace)]
+    for rec, sp in zip(recs, specs):
+        rec.n_comp, rec.mode, rec.sample_sd = sp["n_comp"], sp["mode"], bool(sp["sample_sd"])
     return recs[0] if single else recs
 
 

@@ -37,6 +37,8 @@ from . import hip_backend as hb
 from .physics import *  # noqa: F401,F403  (the reference module does `from physics import *`)
 from .physics import Tau2flux
 
+from .relabel import DEFAULT_MAX_ITER as RELABEL_ROUNDS     # the relabelling that stats / trace / diagnostics(relabel=True) read
+
 FWHM_PER_SIGMA = 2.0 * np.sqrt(2.0 * np.log(2.0))
 
 
@@ -84,15 +86,34 @@ class _EnsembleMCMC:
         self._post = {}            # probs -> PosteriorSummary of the device-unit chain at unit pixel width
         self._pred = None          # PredictiveRecord of the device-unit chain, computed once
         self._loo = None           # LooRecord of the device-unit chain, computed once
+        self._relabel = {}         # max_iter -> RelabelRecord of the device-unit chain
+        self._flat_relabel = {}    # max_iter -> [samples, D] in the caller's units, every sample's lines in label order
+        self._diag_relabel = None  # ChainDiagnostics of the device-unit chain relabelled by relabel()
+        self._same_line_units = True      # the map from device to caller units is the same for every line
 
     def sample(self, iter, burn=0, thin=1, progress_bar=False, **_ignored):
         self._fit._run_sampler(int(iter), int(burn), int(thin))
 
-    def _samples(self, name):
+    def _samples(self, name, relabel=False):
         if name in self._derived:
             src, fn = self._derived[name]
-            return fn(self._samples(src))
-        return self._flat[:, self._names.index(name)].copy()
+            return fn(self._samples(src, relabel))
+        flat = self._relabelled_flat() if relabel else self._flat
+        return flat[:, self._names.index(name)].copy()
+
+    def _relabelled_flat(self, max_iter=RELABEL_ROUNDS):
+        """the caller-unit samples gathered by the relabelling record's permutations.  The unit map is the same for
+        every line (checked when the chain came in), so the caller-unit samples are gathered as they are; were it not,
+        the device-unit chain is gathered and mapped afterwards."""
+        if max_iter not in self._flat_relabel:
+            rec, fit = self.relabel(max_iter), self._fit
+            N, W, _ = rec.perm.shape
+            if self._same_line_units:
+                flat = rec.gather(self._flat.reshape(N, W, -1))
+            else:
+                flat = fit._to_caller(rec.gather(fit._chain_dev))
+            self._flat_relabel[max_iter] = flat.reshape(N * W, -1)
+        return self._flat_relabel[max_iter]
 
     @property
     def _traces(self):
@@ -100,28 +121,39 @@ class _EnsembleMCMC:
         builds thousands of fits whose traces are never read)"""
         return {nm: self._samples(nm) for nm in list(self._names) + list(self._derived)}
 
-    def trace(self, name):
+    def trace(self, name, relabel=False):
+        """the samples of ``name``; ``relabel=True``: of label k for a per-line name, from the relabelled chain
+        (``relabel()``)"""
         if name not in self._names and name not in self._derived:
             raise KeyError(name)
-        return _Trace(self._samples(name))
+        return _Trace(self._samples(name, relabel))
 
-    def stats(self):
+    def stats(self, relabel=False):
         """name -> {'n', 'standard deviation', 'mean', 'quantiles', 'mc error'} as PyMC's ``MCMC.stats()``; an entry is
-        computed when it is read (the harvest of a spectrum reads two numbers per line, vpspectrum.py:400-412)."""
-        return _Stats(self)
+        computed when it is read (the harvest of a spectrum reads two numbers per line, vpspectrum.py:400-412).
+        ``relabel=True``: from the relabelled chain (``relabel()``), where slot k is the same line in every sample."""
+        return _Stats(self, relabel)
 
-    def diagnostics(self):
+    def diagnostics(self, relabel=False):
         """name -> {'autocorrelation time', 'n_eff', 'r_hat', 'reliable'} for every trace (derived ones included), from
         the GPU (vamp_amd.diagnostics), computed once per fit.  The autocorrelation time is in sampler steps (kept
         samples x thin); n_eff counts samples of the whole ensemble.  Both are invariant under the affine map from the
         device's units to the caller's, and est_sigma_k is linear in est_G_k, so one call on the device-unit chain
-        covers every trace."""
-        if self._diag is None:
-            if self._fit._chain_dev is None:
-                raise RuntimeError("no chain: run the sampler first")
-            from .diagnostics import chain_diagnostics
-            self._set_diagnostics(chain_diagnostics(self._fit._chain_dev, thin=self._thin, device=self._fit.device))
-        d = self._diag
+        covers every trace.  ``relabel=True``: of the relabelled chain (``relabel()``), cached beside the other."""
+        if relabel:
+            if self._diag_relabel is None:
+                rec = self.relabel()
+                from .diagnostics import chain_diagnostics
+                self._set_diagnostics(chain_diagnostics(rec.gather(self._fit._chain_dev), thin=self._thin, device=self._fit.device),
+                                      relabel=True)
+            d = self._diag_relabel
+        else:
+            if self._diag is None:
+                if self._fit._chain_dev is None:
+                    raise RuntimeError("no chain: run the sampler first")
+                from .diagnostics import chain_diagnostics
+                self._set_diagnostics(chain_diagnostics(self._fit._chain_dev, thin=self._thin, device=self._fit.device))
+            d = self._diag
         out = {}
         for i, nm in enumerate(self._names):
             out[nm] = {"autocorrelation time": float(d.tau[i]) * d.thin, "n_eff": float(d.n_eff[i]),
@@ -130,8 +162,11 @@ class _EnsembleMCMC:
             out[nm] = dict(out[src])
         return out
 
-    def _set_diagnostics(self, record):
-        self._diag = record
+    def _set_diagnostics(self, record, relabel=False):
+        if relabel:
+            self._diag_relabel = record
+        else:
+            self._diag = record
 
     def _posterior(self, probs):
         """the fit's PosteriorSummary at unit pixel width for ``probs`` (vamp_amd.posterior), computed once per fit and
@@ -214,12 +249,37 @@ class _EnsembleMCMC:
     def _set_loo(self, record):
         self._loo = record
 
+    def relabel(self, max_iter=RELABEL_ROUNDS):
+        """The fit's ``RelabelRecord`` (vamp_amd.relabel): for every kept sample the permutation of its lines that lies
+        closest to the reference labelling -- the fit's current point, which is the MAP when ``map_estimate`` ran --
+        with the reference moved to the relabelled means until nothing changes, at most ``max_iter`` rounds; per label
+        the mean and standard deviation in the device's units, and how many samples were switched.  One GPU call,
+        cached per fit and ``max_iter``.  ``stats``, ``trace`` and ``diagnostics`` read it with ``relabel=True``."""
+        max_iter = int(max_iter)
+        if max_iter not in self._relabel:
+            fit = self._fit
+            if fit._chain_dev is None:
+                raise RuntimeError("no chain: run the sampler first")
+            from . import relabel
+            _, recs = relabel.fits_relabel([fit], max_iter=max_iter, device=fit.device)
+            if max_iter not in self._relabel:  # (fits_relabel fills the cache)
+                self._set_relabel(recs[0])
+        return self._relabel[max_iter]
+
+    def _set_relabel(self, record):
+        key = RELABEL_ROUNDS if record.max_iter is None else int(record.max_iter)
+        self._relabel[key] = record
+        self._flat_relabel.pop(key, None)
+        if key == RELABEL_ROUNDS:      # what diagnostics(relabel=True) was computed from
+            self._diag_relabel = None
+
 
 class _Stats(Mapping):
     """``mcmc.stats()``: a read-only mapping over every trace name whose entries are computed on first access"""
 
-    def __init__(self, mcmc):
+    def __init__(self, mcmc, relabel=False):
         self._mcmc = mcmc
+        self._relabel = bool(relabel)
         self._names = list(mcmc._names) + list(mcmc._derived)
         self._done = {}
 
@@ -233,7 +293,7 @@ class _Stats(Mapping):
         if name not in self._done:
             if name not in self._names:
                 raise KeyError(name)
-            s = self._mcmc._samples(name)
+            s = self._mcmc._samples(name, self._relabel)
             q = np.percentile(s, [2.5, 25, 50, 75, 97.5])
             sd = float(np.std(s))
             self._done[name] = {"n": s.size, "standard deviation": sd, "mean": float(np.mean(s)),
@@ -534,6 +594,10 @@ class VPfit():
         mc_._post = {}
         mc_._pred = None
         mc_._loo = None
+        mc_._relabel, mc_._flat_relabel, mc_._diag_relabel = {}, {}, None
+        q, K = self._q, self._n       # relabelled caller-unit samples are gathered as they are only if every line maps alike
+        mc_._same_line_units = all(np.array_equal(self._scale[:q], self._scale[q * k:q * k + q]) and
+                                   np.array_equal(self._shift[:q], self._shift[q * k:q * k + q]) for k in range(K))
         if self._voigt:      # the reference's callers ask for est_sigma_k in Voigt mode too (vpspectrum.py:400)
             for k in range(self._n):
                 mc_._derived["est_sigma_%d" % k] = ("est_G_%d" % k, self.GaussianWidth)

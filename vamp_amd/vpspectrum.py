@@ -540,6 +540,62 @@ class VPspectrum():
         h5min.write(path, {k: np.array(v) for k, v in rec.items()})
         return path
 
+    def relabel(self, max_iter=None):
+        """After ``fit_spectrum`` (batched or not): the relabelling that undoes label switching, of every kept fit from
+        ONE GPU call over their chains (vamp_amd.relabel; each fit's ``mcmc.relabel()`` cache is filled), and the
+        largest R-hat of every region before and after it from two diagnostics calls.  A dict, per region [n_regions]:
+        ``n_iter`` / ``n_changed`` / ``n_switched`` / ``n_used`` / ``n_bad`` / ``n_comp`` (int32), ``converged`` (int8),
+        ``max_r_hat_before`` / ``max_r_hat_after``, ``min_n_eff_before`` / ``min_n_eff_after`` (NaN for a chain too long for
+        the diagnostics) and ``tau_reliable_before`` / ``tau_reliable_after`` (int8; is every parameter's tau reliable?); per
+        line, region after region, ``label_mean`` / ``label_sd`` [n_lines, q] in the caller's units with ``line_region`` [n_lines]."""
+        from . import diagnostics, relabel
+        max_iter = relabel.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
+        regs = self.regions
+        fits = [r.fit for r in regs]
+        device = getattr(self, "device", 0)
+        have, recs = relabel.fits_relabel(fits, max_iter=max_iter, device=device)
+        if len(have) != len(regs):
+            raise RuntimeError("relabel: %d of %d regions have no chain" % (len(regs) - len(have), len(regs)))
+        diagnostics.fits_diagnostics(fits, device=device)
+        ok = [i for i, f in enumerate(fits) if f._chain_dev.shape[0] <= diagnostics.MAX_SAMPLES]
+        after = diagnostics.chain_diagnostics([recs[i].gather(fits[i]._chain_dev) for i in ok], thin=[fits[i].mcmc._thin for i in ok],
+                                              device=device) if ok else []
+        if max_iter == relabel.DEFAULT_MAX_ITER:       # the relabelling a fit's diagnostics(relabel=True) reads
+            for i, d in zip(ok, after):
+                fits[i].mcmc._set_diagnostics(d, relabel=True)
+        worst = lambda d: float(np.nanmax(d.r_hat)) if d is not None and np.any(~np.isnan(d.r_hat)) else np.nan
+        least = lambda d: float(np.nanmin(d.n_eff)) if d is not None and np.any(~np.isnan(d.n_eff)) else np.nan
+        sure = lambda d: int(d is not None and bool(np.all(d.reliable)))
+        out = {k: np.array([getattr(r, k) for r in recs], dtype=np.int32) for k in ("n_iter", "n_changed", "n_switched", "n_used", "n_bad")}
+        out["converged"] = np.array([r.converged for r in recs], dtype=np.int8)
+        out["n_comp"] = np.array([f._n for f in fits], dtype=np.int32)
+        out["max_r_hat_before"] = np.array([worst(f.mcmc._diag if i in ok else None) for i, f in enumerate(fits)], dtype=np.float64)
+        by_region = dict(zip(ok, after))
+        out["max_r_hat_after"] = np.array([worst(by_region.get(i)) for i in range(len(fits))], dtype=np.float64)
+        first = [f.mcmc._diag if i in ok else None for i, f in enumerate(fits)]
+        then = [by_region.get(i) for i in range(len(fits))]
+        out["min_n_eff_before"], out["min_n_eff_after"] = (np.array([least(d) for d in ds], dtype=np.float64) for ds in (first, then))
+        out["tau_reliable_before"], out["tau_reliable_after"] = (np.array([sure(d) for d in ds], dtype=np.int8) for ds in (first, then))
+        q = max([r.label_mean.shape[1] for r in recs], default=3)
+        mean, sd, owner = [], [], []
+        for i, (f, r) in enumerate(zip(fits, recs)):
+            qf = r.label_mean.shape[1]
+            scale, shift = np.asarray(f._scale)[:qf], np.asarray(f._shift)[:qf]
+            m, s = np.full((r.label_mean.shape[0], q), np.nan), np.full((r.label_mean.shape[0], q), np.nan)
+            m[:, :qf], s[:, :qf] = r.label_mean * scale + shift, r.label_sd * np.abs(scale)
+            mean.append(m); sd.append(s); owner += [i] * len(m)
+        out["label_mean"] = np.concatenate(mean) if mean else np.zeros((0, q))
+        out["label_sd"] = np.concatenate(sd) if sd else np.zeros((0, q))
+        out["line_region"] = np.array(owner, dtype=np.int32)
+        return out
+
+    def write_relabel(self, rec):
+        """``relabel()``'s dict as ``<prefix>relabel.h5`` through vamp_amd/h5min.py; returns the path"""
+        from . import h5min
+        path = self.output_filename + 'relabel.h5'
+        h5min.write(path, {k: np.array(v) for k, v in rec.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
