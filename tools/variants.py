@@ -11,6 +11,12 @@ Switches of the far-field tile loop that have a build of their own (see the #ifn
   mom0=-DVAMP_TILE_MOMENTS=0     every tile pixel by pixel
   np0=-DVAMP_NODE_PASS=0         the node stage tile by tile from the tiles' far and wide lists (default 1: line by line over a
                                  full batch of four tiles, lane = (tile, node))
+  runs0=-DVAMP_NP_CLASS_RUNS=0   the node pass as one loop that picks pair and depth per iteration and reads a line's record only on the
+                                 lanes it is far for (default 1: one counted loop per depth, its constants read once ahead of it, the
+                                 records of a pair read by every lane one pair ahead)
+  tab2=-DVAMP_TAB_PAIR=1         in-zone near lines: the Taylor table for two pixels of a lane at a time (default 0: measured, slower)
+  head1=-DVAMP_TILE_HEAD=1       a tile's abscissae requested after the test that it is done from its moments (default 0: measured,
+                                 inside the runs' spread)
 """
 import json
 import os

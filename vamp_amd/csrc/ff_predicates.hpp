@@ -21,4 +21,39 @@ VAMP_DEV bool ff_tile_in_zone(double c, double s, double y, double mid, double h
     return fma(Xf, Xf, y * y) < R2_CORE * (1.0 - FF_ZONE_MARGIN);
 }
 
+// The order in which the node pass of a full batch (ff_node_pass) evaluates the batch's far lines.  The sets are nested,
+// n6 <= n4 <= n3 <= far (bit k: line k needs a fraction of at least that many levels for some tile of the batch).  The
+// lines go deepest class first -- 6, 4, 3, 2 levels -- and by ascending index inside a class; neighbours of that sequence
+// form a pair, a pair runs at the depth of its FIRST member (an odd last line of a class pairs with the first line of the
+// next class, at its own depth), and an odd last line of all pairs with itself.
+//   seq       line indices, four bits each, first line in the lowest nibble; an odd last line stands twice
+//   solo      bit of the line that pairs with itself, 0 when the count is even: the second slot of that pair adds nothing
+//   pairs[d]  consecutive pairs to run at 6, 4, 3 and 2 levels (d = 0 .. 3)
+struct NpOrder {
+    unsigned long long seq;
+    unsigned solo;
+    int pairs[4];
+};
+VAMP_DEV NpOrder np_pair_order(unsigned far, unsigned n6, unsigned n4, unsigned n3) {
+    NpOrder o;
+    const unsigned cls[4] = {n6, n4 & ~n6, n3 & ~n4, far & ~n3};
+    unsigned long long seq = 0ull;
+    int sh = 0, last = 0;
+    for (int c = 0; c < 4; ++c) {
+        for (unsigned m = cls[c]; m; m &= m - 1u) {
+            last = __builtin_ctz(m);
+            seq |= (unsigned long long)last << sh;
+            sh += 4;
+        }
+    }
+    const bool odd = (sh & 4) != 0;
+    if (odd) seq |= (unsigned long long)last << sh;
+    o.seq = seq;
+    o.solo = odd ? 1u << last : 0u;
+    const int h6 = (__builtin_popcount(n6) + 1) >> 1, h4 = (__builtin_popcount(n4) + 1) >> 1, h3 = (__builtin_popcount(n3) + 1) >> 1,
+              hf = (__builtin_popcount(far) + 1) >> 1;
+    o.pairs[0] = h6, o.pairs[1] = h4 - h6, o.pairs[2] = h3 - h4, o.pairs[3] = hf - h3;
+    return o;
+}
+
 }  // namespace vamp

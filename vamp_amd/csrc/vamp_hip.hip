@@ -118,6 +118,15 @@
 #ifndef VAMP_NODE_PASS
 #define VAMP_NODE_PASS 1       // fp64 far-field loop: the node values of a full batch of four tiles line by line, lane = (tile, node)
 #endif                         // (ff_node_pass, sweep_range_ff_np); 0: tile by tile from the tiles' lists (ff_node_sums)
+#ifndef VAMP_NP_CLASS_RUNS
+#define VAMP_NP_CLASS_RUNS 1   // node pass: one counted loop of pairs per depth, its constants read once ahead of it, the records of
+#endif                         // a pair read by every lane one pair ahead (vamp::np_pair_order); 0: depth and pair chosen inside one loop
+#ifndef VAMP_TAB_PAIR
+#define VAMP_TAB_PAIR 0        // in-zone near lines: the Taylor table for two pixels of a lane at a time (table_eval2): measured, off
+#endif                         // (+0.4 % on the headline; profiles/tile_loop_waits_ab.txt); 0: one by one
+#ifndef VAMP_TILE_HEAD
+#define VAMP_TILE_HEAD 0       // fp64 far-field loop: a tile's abscissae requested after the test that it is done from its moments:
+#endif                         // measured, off (-0.2 %, inside the runs' spread; profiles/tile_loop_waits_ab.txt)
 namespace {
 
 constexpr int KMAX = 16;                       // lines per region of the fast shapes (far field, Taylor tables, packing)
@@ -600,6 +609,47 @@ __device__ __forceinline__ double table_eval(const double* tab, double x) {
         r = fma(r, d, c[n].x);
     }
     return r;
+}
+// table_eval for two pixels of a lane: both rows are requested before either Horner chain starts, and the chains go
+// step by step side by side, so that one wait serves both rows and each multiply-add's latency is covered by the
+// other chain's.  Per pixel the operations and their order are table_eval's.
+__device__ __forceinline__ void table_eval2(const double* tab, double x0, double x1, double& r0, double& r1) {
+    constexpr double MAGIC = 6755399441055744.0;
+    constexpr int NP = vamp::TAB_NT / 2;
+    const double x[2] = {x0, x1};
+    double d[2], r[2];
+    double2 c[2][NP];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const double xs = x[p] - 0.5 * vamp::CORE_H;
+        const double t = fma(xs, 2.0, MAGIC);
+        const int i = __double2loint(t);
+        d[p] = fma(t - MAGIC, -vamp::CORE_H, xs);
+        const double2* a = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(tab) + __mul24(i, vamp::TAB_NT * (int)sizeof(double)));
+#pragma unroll
+        for (int n = NP - 1; n >= 0; --n) c[p][n] = a[n];
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) r[p] = fma(c[p][NP - 1].y, d[p], c[p][NP - 1].x);
+#pragma unroll
+    for (int n = NP - 2; n >= 0; --n) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) r[p] = fma(r[p], d[p], c[p][n].y);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) r[p] = fma(r[p], d[p], c[p][n].x);
+    }
+    r0 = r[0], r1 = r[1];
+}
+// the table for the T pixels of a lane as the library was built (VAMP_TAB_PAIR)
+template <int T>
+__device__ __forceinline__ void table_eval_tile(const double* tab, const double (&X)[T], double (&H)[T]) {
+    int t = 0;
+#if VAMP_TAB_PAIR
+#pragma unroll
+    for (; t + 1 < T; t += 2) table_eval2(tab, X[t], X[t + 1], H[t], H[t + 1]);
+#endif
+#pragma unroll
+    for (; t < T; ++t) H[t] = table_eval(tab, X[t]);
 }
 
 // true when pred holds on some active lane of this lane's walker group (LPW lanes; the wavefront when LPW = 64).  The
@@ -1213,6 +1263,9 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             for (int t = 0; t < T; ++t) xn[t] = x[nb + 64 * t + lane];
         }
 #else
+#if VAMP_TILE_HEAD
+        if ((unsigned)farmasks & (unsigned)widemasks & 0xffffu) continue;      // done from its moments: nothing of it is loaded
+#endif
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             xi[t] = x[base + 64 * t + lane];
@@ -1246,8 +1299,7 @@ __device__ __forceinline__ void sweep_range_ff(const RegionDev& R, const typenam
             // straight-line path tile_voigt would find for itself (same function, same arguments, same bits: inside
             // |z| < 8 no cap binds), without the sixteen instructions and four votes it takes to find it
             if (TAB && (((unsigned)zonemasks >> k) & 1u)) {
-#pragma unroll
-                for (int t = 0; t < T; ++t) H[t] = table_eval(tab + k * vamp::TAB_LINE, X[t]);
+                table_eval_tile<T>(tab + k * vamp::TAB_LINE, X, H);
             } else {
                 tile_voigt<T, TAB>(ln, dtab_row<PK>(L, k), X, H, TAB ? tab + k * vamp::TAB_LINE : nullptr, dct + FF_EXP);
             }
@@ -1381,6 +1433,7 @@ __device__ __forceinline__ void ff_classify_batch_np(const LDS& L, const double2
 // clamps, patches and picks the depth from the arguments themselves (the idle argument asks for the shallowest).
 constexpr double FF_X_IDLE = 64.0;          // |z|^2 >= 4096: every fraction's range, and below X_FAR
 static_assert(FF_X_IDLE * FF_X_IDLE >= VAMP_FF_R2_M2 && FF_X_IDLE < vamp::X_FAR, "the idle argument neither deepens a pair nor needs a guard");
+template <int M> struct NpDepth { static constexpr int value = M; };       // the depth of a run of pairs (VAMP_NP_CLASS_RUNS)
 template <bool WIDE, bool GUARD, class LDS>
 __device__ __forceinline__ double ff_node_pass(const LDS& L, const double* __restrict__ dct, const double* tab, int lane_, double mid, double half,
                                                unsigned long long farmasks, unsigned long long widemasks, NodeSets sets) {
@@ -1389,6 +1442,71 @@ __device__ __forceinline__ double ff_node_pass(const LDS& L, const double* __res
     const double xnode = fma(half, dct[FF_MAT + (lane & (FF_NODES - 1))], mid);
     const unsigned far16 = ff_tile_field(farmasks, lane);
     double fs = 0.0;
+#if VAMP_NP_CLASS_RUNS
+    // The pairs in vamp::np_pair_order's order, as one counted loop per depth: the constants of a depth are read once ahead
+    // of its loop and serve both values of every pair of the run.  The records of a pair are read at their wave-uniform
+    // addresses by every lane, one pair ahead of their use, and a lane for whose tile a line is not far selects the idle
+    // argument and a zero amplitude: the values of the branches these replace.  (Past the last pair the sequence holds
+    // zeros: the read ahead takes line 0 and nobody uses it.)
+    if (sets.far != 0u) {       // (a batch without a far line -- every line wide, the prior's walkers -- pays one branch, as before)
+    const vamp::NpOrder ord = vamp::np_pair_order(sets.far, sets.n6, sets.n4, sets.n3);
+    unsigned long long seq = ord.seq;
+    const unsigned far16b = far16 & ~ord.solo;          // the second slot of a line paired with itself adds nothing
+    struct Pair { double c[2], s[2], y[2], amp[2]; };
+    auto read_pair = [&](unsigned long long q) {
+        Pair p;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const LineRec& ln = L.line[(unsigned)(q >> (4 * t)) & 15u];
+            p.c[t] = ln.c, p.s[t] = ln.s, p.y[t] = ln.y, p.amp[t] = ln.amp;
+        }
+        return p;
+    };
+    Pair nxt = read_pair(seq);
+    auto run = [&](auto depth, int npairs, const double* Zt, const double* Ct) {
+        constexpr int M = decltype(depth)::value;
+#pragma unroll 1
+        for (int i = 0; i < npairs; ++i) {
+            const Pair p = nxt;
+            const unsigned k0 = (unsigned)seq & 15u, k1 = (unsigned)(seq >> 4) & 15u;
+            seq >>= 8;
+            nxt = read_pair(seq);
+            const bool mine[2] = {((far16 >> k0) & 1u) != 0u, ((far16b >> k1) & 1u) != 0u};
+            double X[2], amp[2], H[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const double Xl = fabs(xnode - p.c[t]) * p.s[t];
+                X[t] = mine[t] ? Xl : FF_X_IDLE;
+                amp[t] = mine[t] ? p.amp[t] : 0.0;
+            }
+            if constexpr (GUARD) {
+                ff_eval2<true>(X, p.y, H, dct + FF_EXP);
+            } else {
+                const double r2[2] = {fma(X[0], X[0], p.y[0] * p.y[0]), fma(X[1], X[1], p.y[1] * p.y[1])};
+                double n[2], d[2];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) vamp::voigt_jfrac_nd<M>(X[t], p.y[t], r2[t], n[t], d[t], Zt, Ct);
+                const double ra = vamp::rcp_nr(d[0] * d[1]);        // (ff_frac2)
+                H[0] = n[0] * (ra * d[1]);
+                H[1] = n[1] * (ra * d[0]);
+            }
+            fs = fma(amp[0], H[0], fs);
+            fs = fma(amp[1], H[1], fs);
+        }
+    };
+    if constexpr (GUARD) {          // (ff_eval2 picks the depth from the arguments: one run)
+        run(NpDepth<2>{}, ord.pairs[0] + ord.pairs[1] + ord.pairs[2] + ord.pairs[3], nullptr, nullptr);
+    } else {
+        // (the opaque zero stands between a run's constants and the runs before it: read ahead of ITS loop, no earlier)
+        const int z6 = vamp::opaque_zero();
+        run(NpDepth<6>{}, ord.pairs[0], vamp::GHFrac<6>::Z + z6, vamp::GHFrac<6>::C + z6);
+        const int z4 = vamp::opaque_zero();
+        run(NpDepth<4>{}, ord.pairs[1], vamp::GHFrac<4>::Z + z4, vamp::GHFrac<4>::C + z4);
+        run(NpDepth<3>{}, ord.pairs[2], vamp::GHFrac<3>::Z, vamp::GHFrac<3>::C);
+        run(NpDepth<2>{}, ord.pairs[3], vamp::GHFrac<2>::Z, vamp::GHFrac<2>::C);
+    }
+    }
+#else
     unsigned rest = sets.far, n6 = sets.n6, n4 = sets.n4, n3 = sets.n3;
     while (rest) {
         const int depth = n6 ? 6 : n4 ? 4 : n3 ? 3 : 2;
@@ -1426,6 +1544,7 @@ __device__ __forceinline__ double ff_node_pass(const LDS& L, const double* __res
         fs = fma(amp[0], H[0], fs);
         fs = fma(amp[1], H[1], fs);
     }
+#endif
     if constexpr (WIDE) {
         const unsigned wide16 = ff_tile_field(widemasks, lane);
         for (unsigned w = sets.wide; w; w &= w - 1u) {
@@ -1546,12 +1665,17 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
     for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX, zonemasks >>= KMAX) {
         const int base = batch + j * stride;
         double xi[T], tau[T];
+#if VAMP_TILE_HEAD
+        if ((unsigned)farmasks & (unsigned)widemasks & 0xffffu) continue;      // done from its moments: nothing of it is loaded
+#endif
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             xi[t] = x[base + 64 * t + lane];
             tau[t] = 0.0;
         }
+#if !VAMP_TILE_HEAD
         if ((unsigned)farmasks & (unsigned)widemasks & 0xffffu) continue;      // done from its moments
+#endif
         const bool up = __double2hiint(geo[base >> 8].y) >= 0;
         const unsigned farmask = (unsigned)farmasks & 0xffffu;
         const unsigned widemask = WIDE ? (unsigned)widemasks & 0xffffu : 0u;
@@ -1562,8 +1686,7 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
 #pragma unroll
             for (int t = 0; t < T; ++t) X[t] = fabs(xi[t] - ln.c) * ln.s;
             if (TAB && (((unsigned)zonemasks >> k) & 1u)) {
-#pragma unroll
-                for (int t = 0; t < T; ++t) H[t] = table_eval(tab + k * vamp::TAB_LINE, X[t]);
+                table_eval_tile<T>(tab + k * vamp::TAB_LINE, X, H);
             } else {
                 tile_voigt<T, TAB>(ln, dtab_row<PK>(L, k), X, H, TAB ? tab + k * vamp::TAB_LINE : nullptr, dct + FF_EXP);
             }

@@ -255,13 +255,10 @@ VAMP_DEV int opaque_zero() {
 
 // num/den = sqrt(pi) Re w (num carries the factor y).  r2 = x^2 + y^2, y2 = y^2.
 //   D_j = (Re z^2 - zeta_j)^2 + (Im z^2)^2,  N_j = c_j r2 + c_j zeta_j
+// (Zt, Ct: where the poles and residues are read from -- GHFrac<M>::Z / ::C, through whatever offset the caller chose)
 template <int M>
-VAMP_DEV void voigt_jfrac_nd(double x, double y, double r2, double& num, double& den) {
+VAMP_DEV void voigt_jfrac_nd(double x, double y, double r2, double& num, double& den, const double* Zt, const double* Ct) {
     using G = GHFrac<M>;
-    // the two hot branches (2 and 3 levels: 80 % of the evaluations of a long region) keep their
-    // ten constants in registers; the deeper ones reload theirs on entry
-    const double* Zt = G::Z + (M >= 4 ? opaque_zero() : 0);
-    const double* Ct = G::C + (M >= 4 ? opaque_zero() : 0);
     const double y2 = y * y;
     const double zr = fma(x, x, -y2);        // Re z^2
     const double zi2 = (4.0 * y2) * (zr + y2);   // (Im z^2)^2 = 4 x^2 y^2
@@ -283,6 +280,14 @@ VAMP_DEV void voigt_jfrac_nd(double x, double y, double r2, double& num, double&
     }
     num = y * N;
     den = D;
+}
+template <int M>
+VAMP_DEV void voigt_jfrac_nd(double x, double y, double r2, double& num, double& den) {
+    // the two hot branches (2 and 3 levels: 80 % of the evaluations of a long region) keep their
+    // ten constants in registers; the deeper ones reload theirs on entry
+    const double* Zt = GHFrac<M>::Z + (M >= 4 ? opaque_zero() : 0);
+    const double* Ct = GHFrac<M>::C + (M >= 4 ? opaque_zero() : 0);
+    voigt_jfrac_nd<M>(x, y, r2, num, den, Zt, Ct);
 }
 
 template <int M>
