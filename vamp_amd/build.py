@@ -8,7 +8,7 @@ SRC = os.path.join(HERE, "csrc", "vamp_hip.hip")
 OUT = os.path.join(HERE, "libvamp_hip.so")
 # every file vamp_hip.hip #includes: a regenerated matrix or an edited header must trigger a rebuild
 DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("ff_matrix.inc", "ff_matrix32.inc", "voigt_math.hpp", "map_search.hpp", "host_plan.hpp",
-                                                         "abi_state.hpp", "draws.hpp", "ff_predicates.hpp", "ff_moments.hpp")
+                                                         "abi_state.hpp", "draws.hpp", "ff_predicates.hpp", "ff_moments.hpp", "ff_super.inc")
                 if os.path.exists(os.path.join(HERE, "csrc", f))] + [os.path.join(HERE, "..", "include", "vamp_hip.h")]
 
 

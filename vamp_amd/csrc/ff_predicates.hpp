@@ -21,6 +21,62 @@ VAMP_DEV bool ff_tile_in_zone(double c, double s, double y, double mid, double h
     return fma(Xf, Xf, y * y) < R2_CORE * (1.0 - FF_ZONE_MARGIN);
 }
 
+// A line "distant" from a super-tile -- the four adjacent tiles of a batch, [Mid - Half, Mid + Half] from the outer edges
+// of its first and last tile: its centre lies >= VAMP_SUPER_DIST super-tile half-widths beyond the super-tile's edge, and
+// the edge bound of r2 there is at least VAMP_FF_R2_M3, so that no point of the super-tile asks for a fraction deeper than
+// 3 levels.  Such a line is evaluated once at the 16 Chebyshev nodes of the SUPER-tile and interpolated to the tiles' own
+// nodes (VAMP_SUPER_NODES).  The factor is the distance from which a 16-node interpolant reproduces a wing to 4e-15
+// (tests/test_ff_matrix.py); from 2 half-widths it holds only 6e-13, more than the node sums' bar allows.  Every tile of
+// the super-tile lies inside it, so the line is at least as far from each tile, in units of the tile's own half-width
+// too: distant implies the per-tile far predicate wherever r2 >= 300 > 64 does.  NaN compares false.
+#ifndef VAMP_SUPER_DIST
+#define VAMP_SUPER_DIST 4.0
+#endif
+#ifndef VAMP_FF_R2_M3
+#define VAMP_FF_R2_M3 300.0
+#endif
+VAMP_DEV bool ff_super_distant(double c, double s, double y, double Mid, double Half) {
+    const double distS = fabs(Mid - c) - Half;
+    const double Xe = distS * s;
+    return (distS >= VAMP_SUPER_DIST * Half) & (fma(Xe, Xe, y * y) >= VAMP_FF_R2_M3);
+}
+// the edge bound of a distant line: r2 >= this at every point of the super-tile (the depth of its fraction, 3 or 2 levels)
+VAMP_DEV double ff_super_r2e(double c, double s, double y, double Mid, double Half) {
+    const double Xe = (fabs(Mid - c) - Half) * s;
+    return fma(Xe, Xe, y * y);
+}
+// (Mid, Half) of the super-tile whose first and last tile are (mid0, half0) and (mid3, half3), on either direction of the grid
+VAMP_DEV void ff_super_tile(double mid0, double half0, double mid3, double half3, double& Mid, double& Half) {
+    const double lo = fmin(mid0 - half0, mid3 - half3), hi = fmax(mid0 + half0, mid3 + half3);
+    Mid = 0.5 * (lo + hi);
+    Half = 0.5 * (hi - lo);
+}
+
+// The order of a batch's distant lines (bits of `dist`; d3 <= dist: the edge bound is below VAMP_FF_R2_M2, three levels):
+// the three-level lines first, by ascending index inside a class, four bits each, first line in the lowest nibble.  The
+// distant pass takes eight of them per iteration -- slot 4 t + g of iteration i is line 8 i + 4 t + g of the sequence --
+// `iters` iterations in all, the first `iters3` of them at three levels (an iteration that holds one such line).
+struct SuperOrder {
+    unsigned long long seq;
+    int n, iters, iters3;
+};
+VAMP_DEV SuperOrder super_order(unsigned dist, unsigned d3) {
+    SuperOrder o;
+    const unsigned cls[2] = {d3 & dist, dist & ~d3};
+    unsigned long long seq = 0ull;
+    int sh = 0;
+    for (int c = 0; c < 2; ++c)
+        for (unsigned m = cls[c]; m; m &= m - 1u) {
+            seq |= (unsigned long long)__builtin_ctz(m) << sh;
+            sh += 4;
+        }
+    o.seq = seq;
+    o.n = sh >> 2;
+    o.iters = (o.n + 7) >> 3;
+    o.iters3 = (__builtin_popcount(cls[0]) + 7) >> 3;
+    return o;
+}
+
 // The order in which the node pass of a full batch (ff_node_pass) evaluates the batch's far lines.  The sets are nested,
 // n6 <= n4 <= n3 <= far (bit k: line k needs a fraction of at least that many levels for some tile of the batch).  The
 // lines go deepest class first -- 6, 4, 3, 2 levels -- and by ascending index inside a class; neighbours of that sequence

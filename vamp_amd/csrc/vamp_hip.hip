@@ -121,6 +121,15 @@
 #ifndef VAMP_NP_CLASS_RUNS
 #define VAMP_NP_CLASS_RUNS 1   // node pass: one counted loop of pairs per depth, its constants read once ahead of it, the records of
 #endif                         // a pair read by every lane one pair ahead (vamp::np_pair_order); 0: depth and pair chosen inside one loop
+#ifndef VAMP_DEAL_ADJ
+#define VAMP_DEAL_ADJ 1        // node pass: a full batch is four ADJACENT tiles, class p of PARTS takes tiles 16 m + 4 p .. 16 m + 4 p + 3 of
+#endif                         // every whole group of 16 tiles; 0: tiles p, p + 4, p + 8, p + 12.  What no group holds is dealt p, p + 4, ..
+#ifndef VAMP_SUPER_NODES
+#define VAMP_SUPER_NODES 0     // node pass (needs VAMP_DEAL_ADJ): the lines distant from all four tiles of a batch (vamp::ff_super_distant) once at
+#endif                         // the 16 nodes of the batch's super-tile, eight lines per iteration, and interpolated to the tiles' nodes (ff_super_pass).
+                               // Measured, off: -4.5 .. -5.7 % on the headline, but the prior ensemble, whose walkers never take the pass, runs 1.3 - 1.7 %
+                               // slower with it compiled in, chosen inside the one loop or as a copy of the loop of its own (SUPER), and with that copy
+                               // the headline kernel reloads spilled registers inside its loops (profiles/super_nodes_ab.txt)
 #ifndef VAMP_TAB_PAIR
 #define VAMP_TAB_PAIR 0        // in-zone near lines: the Taylor table for two pixels of a lane at a time (table_eval2): measured, off
 #endif                         // (+0.4 % on the headline; profiles/tile_loop_waits_ab.txt); 0: one by one
@@ -1390,7 +1399,16 @@ __device__ __forceinline__ unsigned ff_fold16(unsigned long long m) {       // O
 }
 // the per-batch sets of lines, nested: n6 <= n4 <= n3 <= far (bit k: line k is far for some tile of the batch and the
 // deepest fraction any of those tiles needs has at least that many levels), and the lines wide for some tile
+#if VAMP_SUPER_NODES && VAMP_DEAL_ADJ
+#define VAMP_SUPER_ON 1
+#include "ff_super.inc"                // FF_SUPER_C (tools/gen_ff_super.py)
+// ... and (VAMP_SUPER_NODES) the lines distant from the batch's super-tile (Mid, Half), which are in none of the other
+// sets: dist, and d3 <= dist, those whose edge bound on the super-tile asks for three levels
+struct NodeSets { unsigned far, n6, n4, n3, wide, dist, d3; double Mid, Half; };
+#else
+#define VAMP_SUPER_ON 0
 struct NodeSets { unsigned far, n6, n4, n3, wide; };
+#endif
 // The classification of a FULL batch for the fp64 loop: ff_classify_batch's masks without its lists, plus the depth class
 // of every far pair from r2e = (dist s)^2 + y^2.  Every node of the tile lies inside it, at least `dist` from the line's
 // centre, so r2e is a lower bound of r2 at every node, and a deeper fraction is valid wherever a shallower one is.
@@ -1398,7 +1416,8 @@ struct NodeSets { unsigned far, n6, n4, n3, wide; };
 template <bool WIDE, bool ZONE, class LDS>
 __device__ __forceinline__ void ff_classify_batch_np(const LDS& L, const double2* __restrict__ geo, int K, int lane_, int base, int stride,
                                                      unsigned wide_all, unsigned long long& farmasks, unsigned long long& widemasks,
-                                                     unsigned long long& zonemasks, NodeSets& sets, double& mid, double& half) {
+                                                     unsigned long long& zonemasks, NodeSets& sets, double& mid, double& half,
+                                                     bool super_ok = false) {
     int lane = lane_;
     asm volatile("" : "+v"(lane));
     const int j = lane >> 4, k = lane & (KMAX - 1);
@@ -1424,6 +1443,24 @@ __device__ __forceinline__ void ff_classify_batch_np(const LDS& L, const double2
     sets.wide = ff_fold16(widemasks);
     zonemasks = 0ull;
     if constexpr (ZONE) zonemasks = __ballot(vamp::ff_tile_in_zone(my_c, my_s, my_y, mid, half));
+#if VAMP_SUPER_ON
+    // The batch's four ADJACENT tiles as one super-tile (super_ok: the caller's tiles are adjacent, the walker has neither a
+    // guard bit nor a line wide for every tile).  Line k has the same verdict on all four rows of lanes: one more ballot,
+    // and one for the depth.  A distant line stays in farmasks -- it is far, not near, for the tile loops -- and leaves the
+    // sets of the ordinary pairs; "far for every tile of the batch" is asked of the masks themselves, not of the rounding.
+    sets.dist = sets.d3 = 0u;
+    sets.Mid = sets.Half = 0.0;
+    if (super_ok) {
+        const double2 g0 = geo[base >> 8], g3 = geo[(base + (FF_BATCH - 1) * stride) >> 8];
+        vamp::ff_super_tile(g0.x, fabs(g0.y), g3.x, fabs(g3.y), sets.Mid, sets.Half);
+        const bool my_dist = (k < K) & vamp::ff_super_distant(my_c, my_s, my_y, sets.Mid, sets.Half);
+        const bool my_d3 = my_dist & (vamp::ff_super_r2e(my_c, my_s, my_y, sets.Mid, sets.Half) < VAMP_FF_R2_M2);
+        const unsigned all4 = (unsigned)farmasks & (unsigned)(farmasks >> 16) & (unsigned)(farmasks >> 32) & (unsigned)(farmasks >> 48) & 0xffffu;
+        sets.dist = (unsigned)__ballot(my_dist) & all4;
+        sets.d3 = (unsigned)__ballot(my_d3) & sets.dist;
+        sets.far &= ~sets.dist, sets.n6 &= ~sets.dist, sets.n4 &= ~sets.dist, sets.n3 &= ~sets.dist;
+    }
+#endif
 }
 // The node pass: lane 16 j + n ends with the node sum of (tile j, node n) -- far lines through the fractions, two lines per
 // iteration sharing a reciprocal (ff_frac2), deepest class first, M the class of the deeper of the two; then (WIDE) the
@@ -1434,14 +1471,102 @@ __device__ __forceinline__ void ff_classify_batch_np(const LDS& L, const double2
 constexpr double FF_X_IDLE = 64.0;          // |z|^2 >= 4096: every fraction's range, and below X_FAR
 static_assert(FF_X_IDLE * FF_X_IDLE >= VAMP_FF_R2_M2 && FF_X_IDLE < vamp::X_FAR, "the idle argument neither deepens a pair nor needs a guard");
 template <int M> struct NpDepth { static constexpr int value = M; };       // the depth of a run of pairs (VAMP_NP_CLASS_RUNS)
+#if VAMP_SUPER_ON
+// The distant pass (VAMP_SUPER_NODES): the batch's distant lines (sets.dist, vamp::ff_super_distant) summed at the 16
+// Chebyshev nodes of the batch's SUPER-tile and interpolated to the 64 (tile, node) points, which lane 16 j + n returns
+// for its own.  Lane 16 g + n evaluates at super-node n the lines of group g: slot 4 t + g of the eight lines of an
+// iteration (vamp::super_order), t = 0, 1 sharing a reciprocal as in ff_frac2; three levels while an iteration holds a
+// line that asks for them, then two; a slot past the last line takes the idle argument and a zero amplitude.  The four
+// groups are added in one order on every lane, the 16 sums become Chebyshev coefficients through the constant cosine
+// table FF_SUPER_C (lane k forms c_k; through Sx.coef, which is free until the batch's tile loops), and every lane
+// evaluates Clenshaw's recurrence at t = (xnode - Mid) / Half, the coefficients read at wave-uniform LDS addresses.
+template <class LDS>
+__device__ __forceinline__ double ff_super_pass(const LDS& L, TileScratch& Sx, const double* __restrict__ dct, int lane, double xnode,
+                                                const NodeSets& sets) {
+    const vamp::SuperOrder ord = vamp::super_order(sets.dist, sets.d3);
+    const int n = lane & (FF_NODES - 1), g4 = (lane >> 4) * 4;
+    const double xs = fma(sets.Half, dct[FF_MAT + n], sets.Mid);
+    unsigned long long seq = ord.seq;
+    int left = ord.n;               // lines of the sequence not yet taken
+    double acc = 0.0;
+    auto run = [&](auto depth, int iters) {
+        constexpr int M = decltype(depth)::value;
+#pragma unroll 1
+        for (int i = 0; i < iters; ++i) {
+            const unsigned s32 = (unsigned)seq >> g4;
+            double X[2], y[2], amp[2], r2[2], nn[2], d[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const LineRec& ln = *reinterpret_cast<const LineRec*>(reinterpret_cast<const char*>(L.line) +
+                                                                      __umul24((s32 >> (16 * t)) & 15u, (unsigned)sizeof(LineRec)));
+                const bool live = (g4 >> 2) + 4 * t < left;
+                const double Xl = fabs(xs - ln.c) * ln.s;
+                X[t] = live ? Xl : FF_X_IDLE;
+                y[t] = ln.y;
+                amp[t] = live ? ln.amp : 0.0;
+                r2[t] = fma(X[t], X[t], y[t] * y[t]);
+                vamp::voigt_jfrac_nd<M>(X[t], y[t], r2[t], nn[t], d[t], vamp::GHFrac<M>::Z, vamp::GHFrac<M>::C);
+            }
+            const double ra = vamp::rcp_nr(d[0] * d[1]);        // (ff_frac2)
+            acc = fma(amp[0], nn[0] * (ra * d[1]), acc);
+            acc = fma(amp[1], nn[1] * (ra * d[0]), acc);
+            seq >>= 32;
+            left -= 8;
+        }
+    };
+    run(NpDepth<3>{}, ord.iters3);
+    run(NpDepth<2>{}, ord.iters - ord.iters3);
+    // (g0 + g1) + (g2 + g3) on every lane.  The partners' addresses are formed here, from lane_here(): taken from the
+    // kernel's other cross-lane sums they were spilled in the prologue and reloaded from scratch in every batch
+    {
+        const int me = lane_here();
+        const int a16 = (me ^ 16) << 2, a32 = (me ^ 32) << 2;
+        acc += __hiloint2double(__builtin_amdgcn_ds_bpermute(a16, __double2hiint(acc)), __builtin_amdgcn_ds_bpermute(a16, __double2loint(acc)));
+        acc += __hiloint2double(__builtin_amdgcn_ds_bpermute(a32, __double2hiint(acc)), __builtin_amdgcn_ds_bpermute(a32, __double2loint(acc)));
+    }
+    if (lane < FF_NODES) Sx.coef[lane] = acc;
+    __builtin_amdgcn_wave_barrier();
+    const double2* crow = reinterpret_cast<const double2*>(FF_SUPER_C) + n;
+    const double2* fv = reinterpret_cast<const double2*>(Sx.coef);
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int n2 = 0; n2 < FF_NODES / 2; ++n2) {
+        const double2 m = crow[n2 * FF_NODES], f2 = fv[n2];
+        a0 = fma(m.x, f2.x, a0);
+        a1 = fma(m.y, f2.y, a1);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < FF_NODES) Sx.coef[lane] = a0 + a1;
+    __builtin_amdgcn_wave_barrier();
+    const double t = (xnode - sets.Mid) * vamp::rcp_nr(sets.Half), t2 = t + t;
+    double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = FF_NODES - 1; k >= 1; --k) {
+        const double b = fma(t2, b1, Sx.coef[k] - b2);
+        b2 = b1;
+        b1 = b;
+    }
+    const double p = fma(t, b1, Sx.coef[0] - b2);
+    __builtin_amdgcn_wave_barrier();        // (the tile loops write Sx.coef next)
+    return p;
+}
+#endif
 template <bool WIDE, bool GUARD, class LDS>
 __device__ __forceinline__ double ff_node_pass(const LDS& L, const double* __restrict__ dct, const double* tab, int lane_, double mid, double half,
-                                               unsigned long long farmasks, unsigned long long widemasks, NodeSets sets) {
+                                               unsigned long long farmasks, unsigned long long widemasks, NodeSets sets,
+                                               TileScratch* Sx = nullptr) {
     int lane = lane_;
     asm volatile("" : "+v"(lane));
     const double xnode = fma(half, dct[FF_MAT + (lane & (FF_NODES - 1))], mid);
-    const unsigned far16 = ff_tile_field(farmasks, lane);
     double fs = 0.0;
+#if VAMP_SUPER_ON
+    // (a guard walker has no distant line: ff_classify_batch_np's super_ok)
+    if (sets.dist != 0u) {
+        fs = ff_super_pass(L, *Sx, dct, lane, xnode, sets);
+        farmasks &= ~(sets.dist * 0x0001000100010001ull);      // the ordinary pairs: the lines far for the tile and not distant
+    }
+#endif
+    const unsigned far16 = ff_tile_field(farmasks, lane);
 #if VAMP_NP_CLASS_RUNS
     // The pairs in vamp::np_pair_order's order, as one counted loop per depth: the constants of a depth are read once ahead
     // of its loop and serve both values of every pair of the run.  The records of a pair are read at their wave-uniform
@@ -1603,10 +1728,11 @@ __device__ __forceinline__ void ff_moment_chi_nodes_row(TileScratch& Sx, const d
 }
 // sweep_range_ff with the node stage of every FULL batch done line by line ahead of the batch's tile loops; what is left
 // of the range after its full batches -- all of a range of fewer than FF_BATCH tiles -- goes through sweep_range_ff
-// itself.  Tile order and the per-lane order of the chi additions are sweep_range_ff's.  The near lines, the series,
+// itself.  Without VAMP_DEAL_ADJ tile order and the per-lane order of the chi additions are sweep_range_ff's; with it a
+// class's batches are four adjacent tiles each (see the loop's head), on every shape alike.  The near lines, the series,
 // Horner's rule and the exponentials are its arithmetic; the node values differ by the order of their sums and, where a
 // pair is evaluated deeper than before, by the fractions' own differences (1e-13 of a value).
-template <int MODE, class PK, bool TAB, bool WIDE = false, bool GUARD = true>
+template <int MODE, class PK, bool TAB, bool WIDE = false, bool GUARD = true, bool SUPER = false>
 __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const typename PK::Lds& L, TileScratch& Sx, const double* __restrict__ dct,
                                                   const double* __restrict__ x, const double* __restrict__ f,
                                                   const double* __restrict__ wt, const double* __restrict__ ut,
@@ -1619,15 +1745,33 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
     const int ntile = base0 < base1 ? (base1 - base0 + stride - 1) / stride : 0;
     // (a wavefront's range is wave-uniform, and so are the batch loop's bounds: said here, because where the range comes
     //  from the wavefront's index the compiler takes the loop for a divergent one and keeps its counter in a vector register)
+#if VAMP_DEAL_ADJ
+    // (base0, stride) name class p = base0 / tile of the stride / tile classes of a region whose first tile is pixel 0.  A
+    // whole group of stride / tile batches of FF_BATCH ADJACENT tiles gives the class its p-th batch; the tiles no group
+    // holds, fewer than a group, are the class's p, p + stride, .. of them and go tile by tile through sweep_range_ff.
+    (void)ntile;
+    const int tstride = 64 * T, bstep = FF_BATCH * stride;
+    const int bfull = __builtin_amdgcn_readfirstlane((base1 / bstep) * bstep);                                  // the first tile past the whole groups
+    const int bfirst = FF_BATCH * base0, brest = bfull + base0;
+#else
+    const int tstride = stride, bstep = FF_BATCH * stride;
     const int bfull = __builtin_amdgcn_readfirstlane(base0 + (ntile / FF_BATCH) * (FF_BATCH * stride));       // the first tile past the full batches
-    for (int batch = __builtin_amdgcn_readfirstlane(base0); batch < bfull; batch += FF_BATCH * stride) {
+    const int bfirst = base0, brest = bfull;
+#endif
+    for (int batch = __builtin_amdgcn_readfirstlane(bfirst); batch < bfull; batch += bstep) {
     unsigned long long farmasks, widemasks, zonemasks;
     double fsn;         // node sum of (tile lane >> 4, node lane & 15): one register pair across the batch's tile loops
     {
         NodeSets sets;
         double mid_j, half_j;
-        ff_classify_batch_np<WIDE, TAB>(L, geo, K, lane, batch, stride, (unsigned)wide_all, farmasks, widemasks, zonemasks, sets, mid_j, half_j);
+#if VAMP_SUPER_ON
+        ff_classify_batch_np<WIDE, TAB>(L, geo, K, lane, batch, tstride, (unsigned)wide_all, farmasks, widemasks, zonemasks, sets, mid_j, half_j,
+                                        SUPER);
+        fsn = ff_node_pass<WIDE, GUARD>(L, dct, tab, lane, mid_j, half_j, farmasks, widemasks, sets, &Sx);
+#else
+        ff_classify_batch_np<WIDE, TAB>(L, geo, K, lane, batch, tstride, (unsigned)wide_all, farmasks, widemasks, zonemasks, sets, mid_j, half_j);
         fsn = ff_node_pass<WIDE, GUARD>(L, dct, tab, lane, mid_j, half_j, farmasks, widemasks, sets);
+#endif
     }
 #if VAMP_TILE_MOMENTS == 2
     {   // tiles without a near line (see sweep_range_ff).  The absorption at the nodes and its largest value per tile are
@@ -1641,7 +1785,7 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
         for (int j = 0; j < FF_BATCH; ++j, fm >>= KMAX, wm >>= KMAX) {
             const unsigned farmask = (unsigned)fm & 0xffffu, widemask = WIDE ? (unsigned)wm & 0xffffu : 0u;
             if ((~(farmask | widemask) & ((1u << K) - 1u)) != 0u) continue;
-            const double* mt = mom + ((batch + j * stride) >> 8) * MOM_TILE;
+            const double* mt = mom + ((batch + j * tstride) >> 8) * MOM_TILE;
             const double root_c0 = mt[MOM_RC], root_q0 = mt[MOM_RQ];
             if (!vamp::ff_moments_try(root_c0, root_q0)) continue;
             if (!have_a) {
@@ -1663,7 +1807,7 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
 #endif
 #pragma unroll 1
     for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX, zonemasks >>= KMAX) {
-        const int base = batch + j * stride;
+        const int base = batch + j * tstride;
         double xi[T], tau[T];
 #if VAMP_TILE_HEAD
         if ((unsigned)farmasks & (unsigned)widemasks & 0xffffu) continue;      // done from its moments: nothing of it is loaded
@@ -1735,14 +1879,20 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
         }
     }
     }
-    if (bfull < base1) sweep_range_ff<MODE, PK, TAB, WIDE, GUARD>(R, L, Sx, dct, x, f, wt, ut, geo, lane, bfull, base1, stride, chi, tab, wide_all, mom);
+    if (brest < base1) sweep_range_ff<MODE, PK, TAB, WIDE, GUARD>(R, L, Sx, dct, x, f, wt, ut, geo, lane, brest, base1, stride, chi, tab, wide_all, mom);
 }
 #endif
+#ifndef VAMP_SUPER_ON
+#define VAMP_SUPER_ON 0
+#endif
 // the fp64 far-field sweep of a range as the library was built
-template <int MODE, class PK, bool TAB, bool WIDE, bool GUARD, class... Args>
+// (SUPER: the walker may take the distant pass -- no guard bit, no line wide for every tile; a copy of the loop of its own, as
+//  WIDE and GUARD have)
+template <int MODE, class PK, bool TAB, bool WIDE, bool GUARD, bool SUPER = false, class... Args>
 __device__ __forceinline__ void sweep_range_ff_any(Args&&... args) {
 #if VAMP_NODE_PASS_ON
-    sweep_range_ff_np<MODE, PK, TAB, WIDE, GUARD>(static_cast<Args&&>(args)...);
+    static_assert(!(SUPER && GUARD), "a guard walker keeps the ordinary pass");
+    sweep_range_ff_np<MODE, PK, TAB, WIDE, GUARD, SUPER && VAMP_SUPER_ON>(static_cast<Args&&>(args)...);
 #else
     sweep_range_ff<MODE, PK, TAB, WIDE, GUARD>(static_cast<Args&&>(args)...);
 #endif
@@ -2187,14 +2337,16 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
                 const unsigned long long wide_all = (unsigned long long)(flags & 0xffff);
                 if (VAMP_MID_NODES || wide_all) {
                     if (guard) sweep_range_ff_any<MODE, PK, TAB, true, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
+                    else if (VAMP_SUPER_ON && wide_all == 0ull)
+                        sweep_range_ff_any<MODE, PK, TAB, true, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
                     else sweep_range_ff_any<MODE, PK, TAB, true, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
                 } else {
                     if (guard) sweep_range_ff_any<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
-                    else sweep_range_ff_any<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                    else sweep_range_ff_any<MODE, PK, TAB, false, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
                 }
             } else {
                 if (guard) sweep_range_ff_any<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
-                else sweep_range_ff_any<MODE, PK, TAB, false, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
+                else sweep_range_ff_any<MODE, PK, TAB, false, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
             }
         } else if (TPIX > 1) sweep_range<MODE, PK, TPIX, TAB>(R, L, x, f, wt, lane, base0, full, stride, chi, tab);
         if constexpr (PK::TAIL || TPIX == 1)
@@ -2484,8 +2636,9 @@ __global__ __launch_bounds__(PK::THREADS, (min_waves<F32, PK>())) void k_lnprob(
 template <int MODE>
 __global__ __launch_bounds__(PackSplit::THREADS) void k_dbg_node_sums(const RegionDev* __restrict__ regions, int region, PixPtrs px,
                                                                       const double* __restrict__ theta, double* __restrict__ nodes,
-                                                                      unsigned* __restrict__ sets_out) {
+                                                                      unsigned* __restrict__ sets_out, bool adj_) {
     using PK = PackSplit;
+    const bool adj = VAMP_DEAL_ADJ && adj_;
     __shared__ typename PK::Lds lds[1];
     __shared__ TileScratch scr[PK::WPB];
     __shared__ alignas(16) double dct[ff_table_doubles<false>()];
@@ -2508,25 +2661,29 @@ __global__ __launch_bounds__(PackSplit::THREADS) void k_dbg_node_sums(const Regi
     constexpr int TILE = 64 * TPIX;
     const int K = R.K, base1 = (R.P / TILE) * TILE, stride = PARTS * TILE;
     const int base0 = __builtin_amdgcn_readfirstlane(wave * TILE);
-    int bfull = base0;
+    int bfull = base0, brest = base0;
 #if VAMP_NODE_PASS_ON
+    // adj: the batches of sweep_range_ff_np with VAMP_DEAL_ADJ (four adjacent tiles); else a class's tiles four at a time
     const int ntile = base0 < base1 ? (base1 - base0 + stride - 1) / stride : 0;
-    bfull = __builtin_amdgcn_readfirstlane(base0 + (ntile / FF_BATCH) * (FF_BATCH * stride));
-    for (int batch = base0; batch < bfull; batch += FF_BATCH * stride) {
+    const int tstride = adj ? TILE : stride, bstep = FF_BATCH * stride;
+    bfull = __builtin_amdgcn_readfirstlane(adj ? (base1 / bstep) * bstep : base0 + (ntile / FF_BATCH) * bstep);
+    brest = adj ? bfull + base0 : bfull;
+    for (int batch = adj ? FF_BATCH * base0 : base0; batch < bfull; batch += bstep) {
         unsigned long long farmasks, widemasks, zonemasks;
         NodeSets sets;
         double mid, half;
-        ff_classify_batch_np<true, true>(L, geo, K, lane, batch, stride, wide_all, farmasks, widemasks, zonemasks, sets, mid, half);
+        ff_classify_batch_np<true, true>(L, geo, K, lane, batch, tstride, wide_all, farmasks, widemasks, zonemasks, sets, mid, half,
+                                         adj && !guard && wide_all == 0u);
         const double fs = guard ? ff_node_pass<true, true>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets)
-                                : ff_node_pass<true, false>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets);
-        nodes[((batch + (lane >> 4) * stride) >> 8) * FF_NODES + (lane & (FF_NODES - 1))] = fs;
+                                : ff_node_pass<true, false>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets, &Sx);
+        nodes[((batch + (lane >> 4) * tstride) >> 8) * FF_NODES + (lane & (FF_NODES - 1))] = fs;
         if (lane == 0) {
             unsigned* so = sets_out + (batch >> 8) * 5;
             so[0] = sets.far, so[1] = sets.n6, so[2] = sets.n4, so[3] = sets.n3, so[4] = sets.wide;
         }
     }
 #endif
-    for (int batch = bfull; batch < base1; batch += FF_BATCH * stride) {
+    for (int batch = brest; batch < base1; batch += FF_BATCH * stride) {
         unsigned long long farmasks, widemasks, zonemasks;
         ff_classify_batch<true, false, true>(L, Sx, geo, K, lane, batch, base1, stride, wide_all, farmasks, widemasks, zonemasks);
         for (int j = 0; j < FF_BATCH; ++j, farmasks >>= KMAX, widemasks >>= KMAX) {
@@ -3975,7 +4132,7 @@ long long vampdbg_tile_moments(vamp_ctx* c, double* out) {
 // Chebyshev nodes, sets [tiles x 5] = {far, n6, n4, n3, wide} at the first tile of every batch the line-major pass took
 // (ff_node_pass) and 0xffffffff elsewhere.  Returns the number of full tiles, 0 when the context runs no fp64 far field
 // (fp32, Gaussian lines, no full tile, more than 16 lines), or an error code.
-long long vampdbg_node_sums(vamp_ctx* c, int region, const double* theta, double* nodes, unsigned* sets) {
+static long long dbg_node_sums(vamp_ctx* c, int region, const double* theta, double* nodes, unsigned* sets, bool adj) {
     if (!c || !theta || !nodes || !sets) return fail(VAMP_ERR_ARG, "vampdbg_node_sums: bad argument");
     if (c->regions_h.empty()) return fail(VAMP_ERR_STATE, "vampdbg_node_sums: call vamp_set_regions first");
     if (region < 0 || region >= c->n_regions) return fail(VAMP_ERR_ARG, "vampdbg_node_sums: no such region");
@@ -3994,15 +4151,26 @@ long long vampdbg_node_sums(vamp_ctx* c, int region, const double* theta, double
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->mode == VAMP_VOIGT4)
         hipLaunchKernelGGL((k_dbg_node_sums<VAMP_VOIGT4>), dim3(1), dim3(PackSplit::THREADS), 0, c->stream, c->regions_d.get(), region, c->pix(),
-                           th_d.get(), nodes_d.get(), sets_d.get());
+                           th_d.get(), nodes_d.get(), sets_d.get(), adj);
     else
         hipLaunchKernelGGL((k_dbg_node_sums<VAMP_NBZ3>), dim3(1), dim3(PackSplit::THREADS), 0, c->stream, c->regions_d.get(), region, c->pix(),
-                           th_d.get(), nodes_d.get(), sets_d.get());
+                           th_d.get(), nodes_d.get(), sets_d.get(), adj);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(nodes, nodes_d.get(), tiles * FF_NODES * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(sets, sets_d.get(), tiles * 5 * sizeof(unsigned), hipMemcpyDeviceToHost));
     return tiles;
+}
+// 1 when the library was built with the distant pass (VAMP_SUPER_NODES and VAMP_DEAL_ADJ): what the hook below then runs
+int vampdbg_super_nodes(void) { return VAMP_SUPER_ON; }
+long long vampdbg_node_sums(vamp_ctx* c, int region, const double* theta, double* nodes, unsigned* sets) {
+    return dbg_node_sums(c, region, theta, nodes, sets, false);
+}
+// ... with the batches as the loop deals them when it was built with VAMP_DEAL_ADJ: four adjacent tiles, the tiles past the
+// last whole group of 16 through the tile-by-tile stage.  Returns 0 when the library was built without the switch.
+long long vampdbg_node_sums_adj(vamp_ctx* c, int region, const double* theta, double* nodes, unsigned* sets) {
+    if (!(VAMP_DEAL_ADJ && VAMP_NODE_PASS_ON)) return 0;
+    return dbg_node_sums(c, region, theta, nodes, sets, true);
 }
 
 int vamp_version(void) { return VAMP_ABI_VERSION; }
