@@ -120,3 +120,25 @@ if __name__ == "__main__":
     print("// TAB32_ECON (fp32 tables: 12 -> 8 coefficients), by parity")
     for n, row in zip(range(8, 12), economisation_matrix(8, 12)):
         print("    {" + ", ".join("%.17e" % float(row[(n & 1) + 2 * m]) for m in range(4)) + "},")
+
+
+def gh_nodes_squared(m, dps=50):
+    """the same poles and residues for any m from the 2m-point Gauss-Hermite rule itself (Golub-Welsch: eigenvalues of
+    its Jacobi matrix, weights from the eigenvectors' first components): zeta_j = t_j^2 over the positive nodes,
+    c_j = 2 w_j / sqrt(pi).  voigt_grad.hpp's GRAD_Z / GRAD_C are m = 12."""
+    import mpmath as mp
+    mp.mp.dps = dps
+    n = 2 * m
+    J = mp.zeros(n)
+    for k in range(1, n):
+        J[k - 1, k] = J[k, k - 1] = mp.sqrt(mp.mpf(k) / 2)
+    E, Q = mp.eigsy(J)
+    return sorted((E[i] ** 2, 2 * Q[0, i] ** 2) for i in range(n) if E[i] > 0)
+
+
+if __name__ == "__main__":
+    import mpmath as mp
+    pf = gh_nodes_squared(12)
+    print("// voigt_grad.hpp: m = 12, sum c =", float(sum(c for _, c in pf)))
+    print("GRAD_Z = {" + ", ".join(mp.nstr(z, 18) for z, _ in pf) + "}")
+    print("GRAD_C = {" + ", ".join(mp.nstr(c, 18) for _, c in pf) + "}")

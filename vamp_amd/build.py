@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-s
 # diagnostics -- the lane-group evaluator (lane_group.hpp); the posterior, the predictive density and PSIS-LOO also the
 # chain checks and the pass planner (chain_groups.hpp): an edit of a shared header rebuilds what includes it
 SIDE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
-POST_FLAGS = EVID_FLAGS = PRED_FLAGS = LOO_FLAGS = RELABEL_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
+POST_FLAGS = EVID_FLAGS = PRED_FLAGS = LOO_FLAGS = RELABEL_FLAGS = FISHER_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
 SIDE_CALL = os.path.join(HERE, "csrc", "side_call.hpp")
 LANE_GROUP = os.path.join(HERE, "csrc", "lane_group.hpp")
 CHAIN_GROUPS = os.path.join(HERE, "csrc", "chain_groups.hpp")
@@ -67,6 +67,14 @@ LOO_DEPS = [LOO_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, os.path.join(HERE, "cs
 RELABEL_SRC = os.path.join(HERE, "csrc", "relabel.hip")
 RELABEL_OUT = os.path.join(HERE, "libvamp_relabel.so")
 RELABEL_DEPS = [RELABEL_SRC, SIDE_CALL, os.path.join(HERE, "csrc", "relabel_host.hpp"), os.path.join(HERE, "..", "include", "vamp_relabel.h")]
+
+# libvamp_fisher.so (include/vamp_fisher.h): gradient, information matrix and covariance at given points from the
+# analytic Jacobian, an eighth library on the same terms; it shares the evaluator (voigt_math.hpp) with the main library
+# and adds the derivative evaluator (voigt_grad.hpp)
+FISHER_SRC = os.path.join(HERE, "csrc", "fisher.hip")
+FISHER_OUT = os.path.join(HERE, "libvamp_fisher.so")
+FISHER_DEPS = [FISHER_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "csrc", "voigt_grad.hpp"),
+               os.path.join(HERE, "..", "include", "vamp_fisher.h")]
 
 
 def _compile(out, src, deps, flags, force, verbose):
@@ -113,14 +121,20 @@ def build_relabel(force=False, verbose=True, out=None, defines=()):
     return _compile(out or RELABEL_OUT, RELABEL_SRC, RELABEL_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
+def build_fisher(force=False, verbose=True, out=None, defines=()):
+    """libvamp_fisher.so; returns its path.  ``out`` / ``defines``: a variant build beside it"""
+    return _compile(out or FISHER_OUT, FISHER_SRC, FISHER_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
+
+
 def build(force=False, verbose=True):
-    """The seven libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
+    """The eight libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
     build_diag(force=force, verbose=verbose)
     build_post(force=force, verbose=verbose)
     build_evid(force=force, verbose=verbose)
     build_pred(force=force, verbose=verbose)
     build_loo(force=force, verbose=verbose)
     build_relabel(force=force, verbose=verbose)
+    build_fisher(force=force, verbose=verbose)
     return _compile(OUT, SRC, DEPS, FLAGS, force, verbose)
 
 

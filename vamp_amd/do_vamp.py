@@ -109,6 +109,12 @@ def fit_one(path, args, device=0):
         if args.output_folder is not None and getattr(spec, "output_filename", None):
             spec.write_loo(loo)
         rec["loo_seconds"] = time.perf_counter() - t1
+    if getattr(args, "fisher", False):
+        t1 = time.perf_counter()
+        fish = spec.fisher()
+        if args.output_folder is not None and getattr(spec, "output_filename", None):
+            spec.write_fisher(fish)
+        rec["fisher_seconds"] = time.perf_counter() - t1
     print("vamp_perf " + json.dumps(rec), flush=True)
     if args.output_folder is not None and getattr(spec, "output_filename", None):
         with open(spec.output_filename + "perf.json", "w") as fh:
@@ -174,6 +180,10 @@ def main(argv=None, _fit_name="vamp_amd.do_vamp:fit_one"):
     p.add_argument("--loo", action="store_true",
                    help="also compute the Pareto-smoothed leave-one-out predictive density (PSIS-LOO) and the Pareto shape khat "
                         "of every pixel of every kept fit from its chain on the GPU, written to <prefix>loo.h5 (off by default)")
+    p.add_argument("--fisher", action="store_true",
+                   help="also compute Fisher-matrix errors of every kept fit at the point it ended on (analytic Jacobian on the "
+                        "GPU, no chain needed): 1-sigma errors per line, status and ln det per region, written to "
+                        "<prefix>fisher.h5 (off by default; params.h5 is not changed)")
     p.add_argument("--relabel", action="store_true",
                    help="also undo label switching in the chains of the kept fits on the GPU: per region how many samples were "
                         "switched and the largest R-hat before and after, per line the mean and standard deviation of its "

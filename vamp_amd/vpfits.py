@@ -440,6 +440,7 @@ class VPfit():
         self._theta_dev[0::self._q][:self._n] = 0.5
         self._chain_dev = None
         self._lnp_chain = None
+        self._fisher = None           # (point key, FisherRecord) of fisher(), for the point it was computed at
         self._set_values(self._theta_dev)
 
     # -- helpers ---------------------------------------------------------------------------
@@ -681,6 +682,22 @@ class VPfit():
         ensemble when there is one); keywords as ``evidence.log_evidence``.  The record is kept as ``self.evidence``."""
         from . import evidence
         return evidence.fits_evidence([self], device=self.device, **kw)[0]
+
+    def fisher(self, with_prior=True):
+        """The fit's ``FisherRecord`` (vamp_amd.fisher) at its current point -- after ``map_estimate`` the MAP, where it is
+        the error estimate a line fitter reports: gradient of the log-posterior, Gauss-Newton information matrix, its
+        inverse ``cov`` and ``sigma`` = sqrt(diag cov), in the caller's units and named like the traces.  It needs no
+        chain.  One GPU call, cached per fit until the point moves."""
+        key = (np.asarray(self._theta_dev, dtype=np.float64).tobytes(), bool(with_prior))
+        if getattr(self, "_fisher", None) is None or self._fisher[0] != key:
+            from . import fisher
+            recs = fisher.fits_fisher([self], with_prior=with_prior, device=self.device)
+            if getattr(self, "_fisher", None) is None or self._fisher[0] != key:      # (fits_fisher fills the cache)
+                self._set_fisher(recs[0], with_prior)
+        return self._fisher[1]
+
+    def _set_fisher(self, record, with_prior=True):
+        self._fisher = ((np.asarray(self._theta_dev, dtype=np.float64).tobytes(), bool(with_prior)), record)
 
     def chain_covariance(self, n, voigt=False):
         """Per-component 3x3 covariance of (amplitude, sigma, centroid) samples (vpfits.py:432-456)."""

@@ -596,6 +596,48 @@ class VPspectrum():
         h5min.write(path, {k: np.array(v) for k, v in rec.items()})
         return path
 
+    def fisher(self, with_prior=True):
+        """After ``fit_spectrum`` (batched or not): Fisher-matrix errors of every kept fit at its current point (the MAP
+        the fit ended on) from ONE GPU call (vamp_amd.fisher; each fit's ``fisher()`` cache is filled).  It reads no
+        chain.  A dict; per line, in ``_harvest``'s order and units: ``std_a`` (amplitude), ``std_c`` (centre,
+        wavelength), ``std_s`` (Gaussian sigma, frequency; of a Voigt line that of its G_fwhm) and ``std_L`` (L_fwhm;
+        NaN for a Gaussian line) with ``line_region`` [n_lines]; per region ``status`` (0 ok, 1 information not positive
+        definite, 2 bad point), ``logdet`` (ln det of the information in the caller's units), ``chi2``, ``grad_norm``
+        (the largest |gradient| sqrt(cov_dd): how far from stationary the point is, in sigmas) and ``n_comp``
+        [n_regions]."""
+        from . import fisher
+        fits = [r.fit for r in self.regions]
+        recs = fisher.fits_fisher(fits, with_prior=with_prior, device=getattr(self, "device", 0))
+        cols = {k: [] for k in ("std_a", "std_c", "std_s", "std_L")}
+        owner = []
+        for i, (f, r) in enumerate(zip(fits, recs)):
+            q = f._q
+            ev = f.estimated_variables
+            for k in range(f._n):
+                sg = r.sigma[q * k:q * k + q]
+                nu = ev[k]['centroid'].value
+                cols["std_a"].append(sg[0])
+                cols["std_c"].append(Freq2wave(nu) * sg[1] / nu)           # lambda = c / nu
+                cols["std_s"].append(VPfit.GaussianWidth(sg[3]) if f._voigt else sg[2])
+                cols["std_L"].append(sg[2] if f._voigt else np.nan)
+                owner.append(i)
+        out = {k: np.array(v, dtype=np.float64) for k, v in cols.items()}
+        out["line_region"] = np.array(owner, dtype=np.int32)
+        out["status"] = np.array([r.status for r in recs], dtype=np.int32)
+        out["logdet"] = np.array([r.logdet for r in recs], dtype=np.float64)
+        out["chi2"] = np.array([r.chi2 for r in recs], dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            out["grad_norm"] = np.array([np.max(np.abs(r.grad) * r.sigma) if r.status == 0 else np.nan for r in recs], dtype=np.float64)
+        out["n_comp"] = np.array([f._n for f in fits], dtype=np.int32)
+        return out
+
+    def write_fisher(self, rec):
+        """``fisher()``'s dict as ``<prefix>fisher.h5`` through vamp_amd/h5min.py; returns the path"""
+        from . import h5min
+        path = self.output_filename + 'fisher.h5'
+        h5min.write(path, {k: np.array(v) for k, v in rec.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
