@@ -1,12 +1,15 @@
-"""The host half that libvamp_post.so and libvamp_pred.so share (vamp_amd/csrc/chain_groups.hpp), through a stand-alone
+"""The host half that libvamp_post.so, libvamp_pred.so and libvamp_loo.so share (vamp_amd/csrc/chain_groups.hpp), through a stand-alone
 program (tests/host/chain_groups_host.cpp) built with AddressSanitizer and UBSan:
 
   * plan_passes against a restatement of the greedy rule, and against the properties the GPU tests
     test_pass_packing_does_not_change_a_bit / test_packing_and_group_order_do_not_change_a_bit rest on: every group's
     ranges tile its pixels once and in order, no pass exceeds the cap, is empty, or closes while the next column would
     still fit, offsets are the running sums and scratch_len is the largest pass;
-  * check_chain_groups: every shared message, byte for byte, and what it hands back for groups that pass.
+  * check_chain_groups: every shared message, byte for byte, and what it hands back for groups that pass;
+  * check_chain_data (the predictive and LOO libraries): every data message, byte for byte, after the shared checks, and
+    tot_noise; pack_chain_data: the offsets, every value in its place, nothing for a group without noise.
 """
+import math
 import os
 import subprocess
 
@@ -162,6 +165,61 @@ def test_what_the_checks_hand_back(program):
     out = program(["check %d 3 %s" % (scratch, " ".join(groups)) for scratch in (0, 8 * 16384, 8 * 16384 + 7, 1 << 40)])
     tail = " 16384 11 16464 | 40 6 | 40 13 | 16384 128"
     assert out == ["ok %d" % cap + tail for cap in ((256 << 20) // 8, 16384, 16384, (1 << 40) // 8)]
+
+
+# ---- the data checks and the packing ------------------------------------------------------------------------------
+def data_group(flux_null=0, noise_given=None, bad_flux=-1, flux_value="nan", bad_noise=-1, noise_value="0", **chain):
+    """a group of the chain checks with its data: a noise is given exactly when the sd is not sampled, unless told"""
+    given = int(not chain.get("sd", 0)) if noise_given is None else noise_given
+    return group(**chain) + " %d %d %d %s %d %s" % (flux_null, given, bad_flux, flux_value, bad_noise, noise_value)
+
+
+AT1 = FN + "group 1: "
+DATA_MESSAGES = [
+    ([data_group(), data_group(flux_null=1)], AT1 + "NULL flux"),
+    ([data_group(), data_group(sd=1, ld=28, noise_given=1)], AT1 + "noise must be NULL when sample_sd is set: the chain's sd is the noise"),
+    ([data_group(), data_group(noise_given=0)], AT1 + "NULL noise without sample_sd"),
+    ([data_group(), data_group(bad_flux=5, flux_value="nan")], AT1 + "the flux is not finite at pixel 5"),
+    ([data_group(), data_group(bad_flux=6, flux_value="-inf")], AT1 + "the flux is not finite at pixel 6"),
+    ([data_group(), data_group(bad_noise=4, noise_value="0")], AT1 + "the noise is not finite and positive at pixel 4"),
+    ([data_group(), data_group(bad_noise=0, noise_value="-1")], AT1 + "the noise is not finite and positive at pixel 0"),
+    ([data_group(), data_group(bad_noise=6, noise_value="inf")], AT1 + "the noise is not finite and positive at pixel 6"),
+    ([data_group(), data_group(bad_noise=2, noise_value="nan")], AT1 + "the noise is not finite and positive at pixel 2"),
+    ([data_group(bad_flux=3)], AT + "the flux is not finite at pixel 3"),
+    # the order within a group and between groups: flux pointer, noise form, then pixel by pixel flux before noise
+    ([data_group(bad_noise=1), data_group(flux_null=1)], AT + "the noise is not finite and positive at pixel 1"),
+    ([data_group(flux_null=1, noise_given=0)], AT + "NULL flux"),
+    ([data_group(noise_given=0, bad_flux=0)], AT + "NULL noise without sample_sd"),
+    ([data_group(bad_flux=2, bad_noise=1)], AT + "the noise is not finite and positive at pixel 1"),
+    ([data_group(bad_flux=2, bad_noise=2)], AT + "the flux is not finite at pixel 2"),
+    # a shared rule wins over a data rule, also one of a later group
+    ([data_group(flux_null=1, mode=3)], AT + "mode must be 0 (GAUSS3) or 1 (VOIGT4)"),
+    ([data_group(flux_null=1), data_group(ld=23)], AT1 + "ld < walkers * ndim"),
+    ([data_group(bad_flux=0, bad_pixel=6)], AT + "the abscissa is not finite at pixel 6"),
+]
+
+
+def test_every_data_message_byte_for_byte_after_the_shared_checks(program):
+    out = program(["data 0 %d %s" % (len(groups), " ".join(groups)) for groups, _ in DATA_MESSAGES])
+    assert out == ["error " + want for _, want in DATA_MESSAGES]
+    out = program(["data %d 1 %s" % (8 * 40 - 1, data_group(flux_null=1))])
+    assert out == ["error " + FN + "scratch_bytes = 319 is less than one column of the largest group (320 bytes)"]
+
+
+def test_data_that_pass_hand_back_the_noise_pixels(program):
+    groups = [data_group(n_pix=3), data_group(n_pix=1, sd=1, ld=28), data_group(n_pix=2)]
+    assert program(["data 0 3 " + " ".join(groups), "data 0 1 " + groups[1], "data 0 1 " + groups[2]]) == ["ok 5", "ok 0", "ok 2"]
+
+
+def test_packing_three_groups_known_noise_free_sd_known_noise(program):
+    P, given = (3, 1, 2), (1, 0, 1)
+    head, values = program(["pack 0 3 " + " ".join("%d %d" % pg for pg in zip(P, given))])[0][len("pack "):].split("|")
+    assert [int(v) for v in head.split()] == [0, 6, 12, 17, 22, 22]        # x | flux | noise | ln noise | end, the vector's size
+    h = [float(v) for v in values.split()]
+    x = [100.0 * g + p + 0.25 for g in range(3) for p in range(P[g])]
+    flux = [-(100.0 * g + p) - 0.5 for g in range(3) for p in range(P[g])]
+    noise = [0.5 + (10.0 * g + p) / 64.0 for g in (0, 2) for p in range(P[g])]     # no slot for the free-sd group
+    assert h == x + flux + noise + [math.log(n) for n in noise]
 
 
 def test_the_libraries_hints_are_todays():

@@ -169,6 +169,18 @@ def test_pointwise_is_from_loglik_of_its_own_matrix_bit_for_bit(evaluated):
         _same(a, b)
 
 
+def test_lppd_and_counts_are_the_predictive_library_s_bit_for_bit(evaluated):
+    """WAIC and PSIS-LOO rest on one l_sp: vamp_pred_pointwise on the same arguments, at the default scratch and at one
+    column of the largest group (S = 129) per pass, returns the lppd, n_used and n_bad of the vamp_loo_pointwise call"""
+    from vamp_amd import predictive
+    groups, flat, _ = evaluated
+    args = _pointwise_args(groups)
+    for scratch in (0, 8 * 129):
+        pred = predictive._call(0, *args, scratch_bytes=scratch)
+        for k in ("lppd", "n_used", "n_bad"):
+            assert pred[k].dtype == flat[k].dtype and np.array_equal(pred[k], flat[k], equal_nan=k not in ref.CNT), (k, scratch)
+
+
 # ---- 4. no bit changes --------------------------------------------------------------------------------------------
 def _run(groups, **kw):
     from vamp_amd.loo import pointwise_loo

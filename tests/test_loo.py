@@ -190,11 +190,11 @@ def test_build_makes_six_libraries_and_leaves_the_other_five_alone():
         assert _exports(path) == _header_functions(stem), stem           # nm -D: what each header declares, nothing of another
     csrc = lambda f: os.path.join(vb.HERE, "csrc", f)
     assert set(vb.LOO_DEPS) == {vb.LOO_SRC, csrc("voigt_math.hpp"), csrc("side_call.hpp"), csrc("lane_group.hpp"), csrc("chain_groups.hpp"),
-                                os.path.join(vb.HERE, "..", "include", "vamp_loo.h")}
+                                csrc("pointwise_ll.hpp"), os.path.join(vb.HERE, "..", "include", "vamp_loo.h")}
     assert vb.LOO_SRC == csrc("loo.hip") and vb.LOO_OUT.endswith("libvamp_loo.so")
     assert vb.LOO_FLAGS == vb.PRED_FLAGS == vb.SIDE_FLAGS and "-fvisibility=hidden" in vb.LOO_FLAGS
     includes = set(re.findall(r'#include "([^"]+)"', open(vb.LOO_SRC).read()))
-    assert includes == {"../../include/vamp_loo.h", "chain_groups.hpp", "lane_group.hpp", "side_call.hpp", "voigt_math.hpp"}
+    assert includes == {"../../include/vamp_loo.h", "chain_groups.hpp", "lane_group.hpp", "pointwise_ll.hpp", "side_call.hpp", "voigt_math.hpp"}
     for name in ("vamp_hip.h", "vamp_diag.h", "vamp_post.h", "vamp_evid.h", "vamp_pred.h"):
         assert "vamp_loo" not in open(os.path.join(ROOT, "include", name)).read()
     assert "vamp_loo" not in open(csrc("predictive.hip")).read()

@@ -163,8 +163,8 @@ def test_build_makes_seven_libraries_and_leaves_the_other_six_alone():
     assert set(vb.DIAG_DEPS) == {vb.DIAG_SRC, csrc("side_call.hpp"), inc("vamp_diag.h")}
     assert set(vb.POST_DEPS) == {vb.POST_SRC, csrc("side_call.hpp"), lane, groups, voigt, inc("vamp_post.h")}
     assert set(vb.EVID_DEPS) == {vb.EVID_SRC, csrc("side_call.hpp"), lane, voigt, csrc("draws.hpp"), inc("vamp_evid.h")}
-    assert set(vb.PRED_DEPS) == {vb.PRED_SRC, csrc("side_call.hpp"), lane, groups, voigt, inc("vamp_pred.h")}
-    assert set(vb.LOO_DEPS) == {vb.LOO_SRC, csrc("side_call.hpp"), lane, groups, voigt, inc("vamp_loo.h")}
+    assert set(vb.PRED_DEPS) == {vb.PRED_SRC, csrc("side_call.hpp"), lane, groups, csrc("pointwise_ll.hpp"), voigt, inc("vamp_pred.h")}
+    assert set(vb.LOO_DEPS) == {vb.LOO_SRC, csrc("side_call.hpp"), lane, groups, csrc("pointwise_ll.hpp"), voigt, inc("vamp_loo.h")}
     assert inc("vamp_hip.h") in vb.DEPS and not any("relabel" in d for d in vb.DEPS)
     for name in ("vamp_hip.h", "vamp_diag.h", "vamp_post.h", "vamp_evid.h", "vamp_pred.h", "vamp_loo.h"):
         assert "vamp_relabel" not in open(inc(name)).read()

@@ -12,7 +12,8 @@
             costs over the WAIC column stage
   numpy     the restatement (tests/loo_ref.py) on every --ref-every-th region, scaled by S K P
 
-python tools/bench_loo.py [--reps 3]"""
+--lib PATH times another build of libvamp_loo.so (vamp_amd.build.build_loo(out=...)), --label names it in the output:
+two builds are compared one process each, in turn.   python tools/bench_loo.py [--reps 3] [--lib PATH --label NAME]"""
 import argparse
 import json
 import os
@@ -29,22 +30,26 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import loo_ref as ref  # noqa: E402
 import predictive_ref  # noqa: E402
 from bench_pred import N_KEEP, W, timed, workload  # noqa: E402
-from vamp_amd import loo, predictive  # noqa: E402
+from vamp_amd import _loo_lib, loo, predictive  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--lib", default=None, help="another build of libvamp_loo.so")
+    ap.add_argument("--label", default="default")
     ap.add_argument("--ref-every", type=int, default=40)
     ap.add_argument("--library-only", action="store_true")
     a = ap.parse_args()
+    if a.lib:
+        _loo_lib.LIB_PATH = os.path.abspath(a.lib)
     dev = torch.device("cuda", 0)
     xs, fluxes, chains, ks = workload()
     G = len(xs)
     S = N_KEEP * W
     pix = int(sum(x.size for x in xs))
     evals = int(sum(S * x.size * k for x, k in zip(xs, ks)))
-    out = {"metric": "psis_loo", "groups": G, "S": S, "tail_length": ref.tail_len(S), "pixels": pix, "lines": int(sum(ks)),
+    out = {"metric": "psis_loo", "label": a.label, "groups": G, "S": S, "tail_length": ref.tail_len(S), "pixels": pix, "lines": int(sum(ks)),
            "voigt_evaluations": evals, "loglik_matrix_bytes": 8 * S * pix}
     common = dict(noises=[None] * G, n_comp=ks, modes=[1] * G, sample_sd=[1] * G, ld=[c.shape[1] * c.shape[2] for c in chains],
                   n_keep=[N_KEEP] * G, walkers=[W] * G)

@@ -1,7 +1,8 @@
 """What the ctypes bindings of the side libraries (``_diag_lib``, ``_post_lib``, ``_evid_lib``, ``_pred_lib``,
-``_loo_lib``, ``_relabel_lib``) and their callers (``diagnostics``, ``posterior``, ``evidence``, ``predictive``, ``loo``,
-``relabel``) share; the second half is what the callers that walk every sample of a chain (``posterior``, ``predictive``,
-``loo``, ``relabel``) hand their libraries alike.
+``_loo_lib``, ``_relabel_lib``, ``_fisher_lib``) and their callers (``diagnostics``, ``posterior``, ``evidence``,
+``predictive``, ``loo``, ``relabel``, ``fisher``) share; the second part is what the callers that walk every sample of a
+chain (``posterior``, ``predictive``, ``loo``, ``relabel``) hand their libraries alike; the third is what the two that
+evaluate the pointwise log-likelihood (``predictive``, ``loo``) do alike around their library call.
 
 The rules of a binding are those of ``_lib``: no fallback (a missing library raises, every call needs a GPU), and
 the library is loaded after torch so that it binds the ROCm runtime torch has mapped -- the one libvamp_hip.so binds
@@ -127,3 +128,91 @@ def chain_args(n_pix, n_comp, modes, sample_sd, bases, is_device, ld, n_keep, wa
     i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
     return [i32(n_pix), i32(n_comp), i32(modes), i32(sample_sd), (C.c_void_p * len(bases))(*[int(b) for b in bases]),
             int(bool(is_device)), np.ascontiguousarray(ld, dtype=np.int64).ctypes.data_as(C.POINTER(C.c_int64)), i32(n_keep), i32(walkers)]
+
+
+# ---- around vamp_pred_pointwise and vamp_loo_pointwise: the data, the outputs, the records ----------------------------
+def data_args(xs, fluxes, noises):
+    """(xs, fluxes, noises) as contiguous fp64 arrays (a noise of None stays None); a group's have one shape"""
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    xs, fluxes = [f64(x) for x in xs], [f64(f) for f in fluxes]
+    noises = [None if n is None else f64(n) for n in noises]
+    for x, f, n in zip(xs, fluxes, noises):
+        if f.shape != x.shape or (n is not None and n.shape != x.shape):
+            raise ValueError("flux and noise must have the abscissa's shape")
+    return xs, fluxes, noises
+
+
+def pointer_array(arrays):
+    """a ``const double* const*`` of host arrays (None: NULL)"""
+    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
+
+
+def outputs(G, tot_pix, want, pix, grp, cnt):
+    """(the output arrays by name, the output arguments in the header's order) of a call over ``G`` groups of ``tot_pix``
+    pixels: of the per-pixel (``pix``), per-group (``grp``) and int32 per-group (``cnt``) names those in ``want`` get
+    an array, the others NULL"""
+    out = {k: np.empty(tot_pix) for k in pix if k in want}
+    out.update({k: np.empty(G) for k in grp if k in want})
+    out.update({k: np.empty(G, dtype=np.int32) for k in cnt if k in want})
+    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    arg = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else None
+    return out, [arg(k, dp) for k in pix + grp] + [arg(k, ip) for k in cnt]
+
+
+def split_records(record, flat, n_pix, steps, pix, grp, cnt):
+    """one ``record(step, **fields)`` per group from a call's flat arrays"""
+    out, op = [], 0
+    for g, (P, st) in enumerate(zip(n_pix, steps)):
+        out.append(record(st, **{k: flat[k][op:op + P].copy() for k in pix}, **{k: float(flat[k][g]) for k in grp},
+                          **{k: int(flat[k][g]) for k in cnt}))
+        op += P
+    return out
+
+
+def pointwise_records(host_call, split, xs, fluxes, noises, chains, n_comp, mode, device, scratch_bytes, steps):
+    """the body of ``pointwise_predictive`` / ``pointwise_loo``: ``host_call`` is the module's ``_pred_host`` / ``_loo_host``,
+    ``split`` its ``_split``"""
+    single = isinstance(chains, np.ndarray)
+    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in ([chains] if single else chains)]
+    xs, fluxes, noises = ([v] if single else list(v) for v in (xs, fluxes, noises))
+    if not len(xs) == len(fluxes) == len(noises) == len(arrays):
+        raise ValueError("one abscissa, one flux and one noise (or None) per chain are required")
+    G = len(arrays)
+    if G == 0:
+        return []
+    n_comp, modes, steps = per_group(n_comp, G, int), per_group(mode, G, int), per_group(steps, G, int)
+    check_chain_shapes(arrays, n_comp, modes, [int(n is None) for n in noises], [f"free sd = {n is None}" for n in noises])
+    flat = host_call(xs, fluxes, noises, arrays, n_comp, modes, steps, int(device), int(scratch_bytes))
+    res = split(flat, [len(x) for x in xs], steps)
+    return res[0] if single else res
+
+
+def context_records(call, split, ctx, chain_ptr, n_keep, xs, fluxes, noises, scratch_bytes):
+    """the body of ``context_predictive`` / ``context_loo``: ``call`` is the module's ``_call``, ``split`` its ``_split``"""
+    ctx.synchronize()                  # the sampler's stream is done with the chain before the default stream reads it
+    if isinstance(xs, np.ndarray) and xs.ndim == 1:
+        xs, fluxes, noises = [xs], [fluxes], [noises]
+    R = len(ctx.ndims)
+    if not len(xs) == len(fluxes) == len(noises) == R:
+        raise ValueError("one abscissa, one flux and one noise (or None) per region of the context are required")
+    ks, modes, sds, bases, ld, n_keep, walkers = context_layout(ctx, chain_ptr, n_keep)
+    for sd, n in zip(sds, noises):
+        if bool(sd) != (n is None):
+            raise ValueError("a region's noise is None exactly when the context samples its sd")
+    flat = call(ctx.device, xs, fluxes, noises, ks, modes, sds, bases, True, ld, n_keep, walkers, scratch_bytes)
+    return split(flat, [len(x) for x in xs], [1] * R)
+
+
+def fits_records(pointwise, setter, fits, device, scratch_bytes):
+    """the body of ``fits_predictive`` / ``fits_loo``: ``pointwise`` is the module's ``pointwise_*``, ``setter`` the name of
+    the method of ``fit.mcmc`` that takes a fit's record"""
+    have = fits_with_chain(fits)
+    if not have:
+        return [], []
+    steps = [time_step(f._chain_dev.shape[0], f._chain_dev.shape[1]) for f in have]
+    recs = pointwise([f._x for f in have], [f._flux for f in have], [None if f._sample_sd else f.noise for f in have],
+                     [f._chain_dev for f in have], [f._n for f in have], [int(f._mode) for f in have], device=device,
+                     scratch_bytes=scratch_bytes, steps=steps)
+    for f, r in zip(have, recs):
+        getattr(f.mcmc, setter)(r)
+    return have, recs

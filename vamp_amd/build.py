@@ -21,12 +21,14 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-s
 
 # The side libraries share their flags, the frame of their entry points (side_call.hpp) and -- all but the
 # diagnostics -- the lane-group evaluator (lane_group.hpp); the posterior, the predictive density and PSIS-LOO also the
-# chain checks and the pass planner (chain_groups.hpp): an edit of a shared header rebuilds what includes it
+# chain checks and the pass planner (chain_groups.hpp), the predictive density and PSIS-LOO the pointwise
+# log-likelihood stage (pointwise_ll.hpp): an edit of a shared header rebuilds what includes it
 SIDE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
 POST_FLAGS = EVID_FLAGS = PRED_FLAGS = LOO_FLAGS = RELABEL_FLAGS = FISHER_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
 SIDE_CALL = os.path.join(HERE, "csrc", "side_call.hpp")
 LANE_GROUP = os.path.join(HERE, "csrc", "lane_group.hpp")
 CHAIN_GROUPS = os.path.join(HERE, "csrc", "chain_groups.hpp")
+POINTWISE_LL = os.path.join(HERE, "csrc", "pointwise_ll.hpp")
 
 # libvamp_diag.so (include/vamp_diag.h): the chain diagnostics, a library of its own with its own dependency list,
 # so that an edit of chain_diag.hip rebuilds it in seconds and leaves the main library alone
@@ -52,14 +54,14 @@ EVID_DEPS = [EVID_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_
 # it shares the evaluator (voigt_math.hpp) with the main library
 PRED_SRC = os.path.join(HERE, "csrc", "predictive.hip")
 PRED_OUT = os.path.join(HERE, "libvamp_pred.so")
-PRED_DEPS = [PRED_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, os.path.join(HERE, "csrc", "voigt_math.hpp"),
+PRED_DEPS = [PRED_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, POINTWISE_LL, os.path.join(HERE, "csrc", "voigt_math.hpp"),
              os.path.join(HERE, "..", "include", "vamp_pred.h")]
 
-# libvamp_loo.so (include/vamp_loo.h): PSIS-LOO, a sixth library on the same terms; its evaluation kernel restates
-# predictive.hip's, so it shares the evaluator (voigt_math.hpp) with the main library too
+# libvamp_loo.so (include/vamp_loo.h): PSIS-LOO, a sixth library on the same terms; it evaluates the log-likelihood
+# with the predictive library's stage, so it shares the evaluator (voigt_math.hpp) with the main library too
 LOO_SRC = os.path.join(HERE, "csrc", "loo.hip")
 LOO_OUT = os.path.join(HERE, "libvamp_loo.so")
-LOO_DEPS = [LOO_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, os.path.join(HERE, "csrc", "voigt_math.hpp"),
+LOO_DEPS = [LOO_SRC, SIDE_CALL, LANE_GROUP, CHAIN_GROUPS, POINTWISE_LL, os.path.join(HERE, "csrc", "voigt_math.hpp"),
             os.path.join(HERE, "..", "include", "vamp_loo.h")]
 
 # libvamp_relabel.so (include/vamp_relabel.h): the relabelling that undoes label switching, a seventh library on the

@@ -1,7 +1,8 @@
 // chain_groups.hpp -- what the libraries that walk every sample of every group's chain over the group's pixels
-// (posterior.hip, predictive.hip) share on the host: the checks of the per-group chain arguments, and the plan that
-// cuts the [S samples] x [P pixels] scratch matrices of all groups into passes.  DESIGN.md "The call frame of the side
-// libraries".
+// (posterior.hip, predictive.hip, loo.hip) share on the host: the checks of the per-group chain arguments, and the plan
+// that cuts the [S samples] x [P pixels] scratch matrices of all groups into passes; for the two that evaluate a
+// log-likelihood (predictive.hip, loo.hip) also the checks and the packing of the data.  DESIGN.md "The call frame of
+// the side libraries".
 //
 // Host code only, and no HIP: tests/host/chain_groups_host.cpp builds it with plain g++.
 #pragma once
@@ -63,6 +64,57 @@ inline std::string check_chain_groups(const std::string& fn, int n_groups, const
         return fn + "scratch_bytes = " + std::to_string(scratch_bytes) + " is less than one column of the largest group (" +
                std::to_string((long long)cg.s_max * (long long)sizeof(double)) + " bytes)";
     return "";
+}
+
+// The checks of the data a log-likelihood is evaluated against (predictive.hip, loo.hip), after check_chain_groups has
+// passed: a flux per group, a noise exactly where the chain does not sample its sd, finite flux, finite positive noise.
+// Returns "" or the message; tot_noise: the pixels of the groups with known noise.
+inline std::string check_chain_data(const std::string& fn, int n_groups, const double* const* flux, const double* const* noise,
+                                    const int32_t* n_pix, const int32_t* sample_sd, long long& tot_noise) {
+    tot_noise = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const std::string at = fn + "group " + std::to_string(g) + ": ";
+        if (!flux[g]) return at + "NULL flux";
+        if (sample_sd[g] && noise[g]) return at + "noise must be NULL when sample_sd is set: the chain's sd is the noise";
+        if (!sample_sd[g] && !noise[g]) return at + "NULL noise without sample_sd";
+        for (int p = 0; p < n_pix[g]; ++p) {
+            if (!std::isfinite(flux[g][p])) return at + "the flux is not finite at pixel " + std::to_string(p);
+            if (noise[g] && !(std::isfinite(noise[g][p]) && noise[g][p] > 0.0))
+                return at + "the noise is not finite and positive at pixel " + std::to_string(p);
+        }
+        tot_noise += noise[g] ? n_pix[g] : 0;
+    }
+    return "";
+}
+
+struct DataOffsets {               // of one vector of doubles: abscissae | data | noise | ln noise
+    long long x = 0, y = 0, noise = 0, ln_noise = 0, end = 0;
+};
+
+// The data of all groups in one vector for one upload, laid out as `off`: a group's pixels side by side in group
+// order; the noise sections hold only the groups with known noise (noise[g] not NULL).
+inline std::vector<double> pack_chain_data(int n_groups, const double* const* x, const double* const* flux, const double* const* noise,
+                                           const int32_t* n_pix, long long tot_pix, long long tot_noise, DataOffsets& off) {
+    off.x = 0;
+    off.y = off.x + tot_pix;
+    off.noise = off.y + tot_pix;
+    off.ln_noise = off.noise + tot_noise;
+    off.end = off.ln_noise + tot_noise;
+    std::vector<double> h((size_t)off.end);
+    long long op = 0, on = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        for (int p = 0; p < n_pix[g]; ++p) {
+            h[off.x + op + p] = x[g][p];
+            h[off.y + op + p] = flux[g][p];
+            if (noise[g]) {
+                h[off.noise + on + p] = noise[g][p];
+                h[off.ln_noise + on + p] = std::log(noise[g][p]);
+            }
+        }
+        op += n_pix[g];
+        on += noise[g] ? n_pix[g] : 0;
+    }
+    return h;
 }
 
 struct Range {                     // pixels p0 .. p0 + np - 1 of a group: an [S] x [np] matrix of the scratch

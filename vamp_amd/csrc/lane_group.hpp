@@ -1,5 +1,5 @@
-// lane_group.hpp -- a group of lanes that owns one parameter vector: what k_post_eval (posterior.hip), k_pred_eval
-// (predictive.hip) and eval_point (evidence.hip) share.  A wavefront -- or, for short regions of few lines, a 16-lane
+// lane_group.hpp -- a group of lanes that owns one parameter vector: what k_post_eval (posterior.hip), k_pointwise_ll
+// (pointwise_ll.hpp) and eval_point (evidence.hip) share.  A wavefront -- or, for short regions of few lines, a 16-lane
 // group -- turns the vector into line records once (centre, scale, damping, amplitude factor, pole factor, h y:
 // line_record below is the record of a chain's sample; the evidence's builder differs and stays in its file), fills
 // the 44-entry near-axis table of every Voigt line (voigt_math.hpp) in LDS, then its lanes walk the pixels.  Also

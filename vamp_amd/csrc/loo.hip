@@ -6,8 +6,8 @@
 // scratch_bytes (chain_groups.hpp, which posterior.hip and predictive.hip share).  The scratch of an item is
 // pixel-major, ll[p * S + s]: what predictive.hip measured as the faster orientation for a column stage that streams
 // its column.  Two launches per pass, one at the end:
-//   k_loo_eval       vamp_loo_pointwise: one workgroup per (item, 64 samples); k_pred_eval of predictive.hip, which is
-//                    not to change with this library, restated here.
+//   k_pointwise_ll   vamp_loo_pointwise: the evaluation this library shares with predictive.hip (pointwise_ll.hpp), one
+//                    workgroup per (item, 64 samples), pixel-major.
 //   k_loo_transpose  vamp_loo_from_loglik: one workgroup per (item, 32 samples) brings the caller's sample-major matrix
 //                    into the same scratch layout through 32 x 32 tiles in LDS.
 //   k_loo_column     one workgroup of 1024 threads per column (a pixel's l over the samples); a thread holds its at most
@@ -33,6 +33,7 @@
 #include "../../include/vamp_loo.h"
 #include "chain_groups.hpp"
 #include "lane_group.hpp"
+#include "pointwise_ll.hpp"
 #include "side_call.hpp"
 #include "voigt_math.hpp"
 
@@ -41,13 +42,8 @@
 namespace {
 
 using namespace vamp::side;
-using vamp::lds_fence;
 
 constexpr bool kNarrow = true;              // a 16-lane group may own a sample: predictive.hip's measurement
-constexpr int kEvalBlock = 256;            // four wavefronts
-constexpr int kEvalWaves = kEvalBlock / 64;
-constexpr int kSamplesPerBlock = 64;
-constexpr int kRec = 6;                    // doubles of a line record
 constexpr int kColBlock = 1024;            // one size for every column: the reduction order must not depend on the pass
 constexpr int kColWaves = kColBlock / 64;
 constexpr int kColPerThread = VAMP_LOO_MAX_SAMPLES / kColBlock;
@@ -60,7 +56,6 @@ constexpr int kIndexBits = 14;             // sample index < 2^14
 constexpr int kTile = 32;                  // the transpose's tile
 constexpr int kTransBlock = 256;
 constexpr int kTotBlock = 64;
-constexpr double HALF_LN_2PI = 0.91893853320467274178;
 constexpr double kHighKhat = 0.7;          // Vehtari, Gelman & Gabry (2017)
 
 static_assert(kColPerThread * kColBlock == VAMP_LOO_MAX_SAMPLES && kColPerThread <= 32, "a thread's entries are a bit mask");
@@ -72,27 +67,10 @@ static_assert((kMaxFit - 30) * (kMaxFit - 30) <= kMaxTail && (kMaxFit - 29) * (k
                   kMaxFit * kFitLanes <= kColBlock,
               "the grid of the fit fits the workgroup");
 
-// LDS of one sample: line records and near-axis tables
-__host__ __device__ constexpr int slot_doubles(int K) { return K * (kRec + vamp::DTAB_N); }
 constexpr size_t kColumnLds = sizeof(double) * (kColBlock + kSortSlots + kMaxTail + kMaxFit * kFitStride + 2 * kMaxFit) +
                               sizeof(int) * (kSortSlots + 2 * kColWaves + 1);
-static_assert((size_t)kEvalWaves * slot_doubles(VAMP_LOO_MAX_COMPONENTS) * sizeof(double) <= 64 * 1024 &&
-                  (size_t)kEvalWaves * (64 / vamp::kNarrowLanes) * slot_doubles(vamp::kNarrowMaxK) * sizeof(double) <= 64 * 1024 &&
-                  kColumnLds <= 64 * 1024 && sizeof(double) * kTile * (kTile + 1) <= 64 * 1024,
+static_assert(VAMP_LOO_MAX_COMPONENTS <= kEvalMaxComponents && kColumnLds <= 64 * 1024 && sizeof(double) * kTile * (kTile + 1) <= 64 * 1024,
               "a launch that asks for more than 64 KiB of LDS needs side::raise_lds_limit");
-
-struct Item {                      // one (group, pixel range) of vamp_loo_pointwise
-    const double* chain;           // the group's chain (device)
-    const double* x;               // the range's abscissa, data and, with known noise, noise and its logarithm (device)
-    const double* y;
-    const double* noise;           // NULL: the sample's sd
-    const double* ln_noise;
-    double* ll;                    // the item's scratch, [np][S]
-    uint8_t* bad;                  // the group's [S] flags
-    long long ld;                  // stride of t, in doubles
-    int W, D, K, q;                // q = 3 (Gauss) or 4 (Voigt) parameters per line
-    int S, np, lanes;              // lanes that own a sample (vamp::group_lanes)
-};
 
 struct Matrix {                    // one (group, pixel range) of vamp_loo_from_loglik
     const double* src;             // the range's first column in the caller's [S][P] matrix (device)
@@ -117,60 +95,6 @@ struct Totals {                    // a group's per-pixel values
     const double* khat;
     int P;
 };
-
-__global__ __launch_bounds__(kEvalBlock) void k_loo_eval(const Item* __restrict__ items, const int2* __restrict__ tasks,
-                                                         int region_doubles) {
-    extern __shared__ double lds[];
-    const int2 task = tasks[blockIdx.x];
-    const Item I = items[task.x];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int lanes = I.lanes;
-    const vamp::LaneGroup lg = vamp::lane_group(lane, lanes);
-    const int nsub = lg.nsub, sub = lg.sub, gl = lg.gl;
-    const int K = I.K;
-    double* rec = lds + (size_t)wave * region_doubles + (size_t)sub * slot_doubles(K);
-    double* dtab = rec + K * kRec;
-    const int s_end = min(task.y + kSamplesPerBlock, I.S);
-    const bool voigt = I.q == 4, free_sd = I.noise == nullptr;
-    const unsigned long long gmask = vamp::group_mask(lanes, sub);
-
-    for (int sb = task.y + wave * nsub; sb < s_end; sb += kEvalWaves * nsub) {      // (uniform per wavefront)
-        const int s = sb + sub;
-        const bool valid = s < s_end;
-        // 1. the sample's line records and its sd, once
-        bool bad_lane = false;
-        double sd = 1.0;
-        if (valid) {
-            const int t = s / I.W, w = s - t * I.W;
-            const double* th = I.chain + (long long)t * I.ld + (long long)w * I.D;
-            if (free_sd) {
-                sd = th[I.D - 1];
-                bad_lane = !isfinite(sd) || sd <= 0.0;
-            }
-            if (gl < K) bad_lane |= vamp::line_record(voigt, th + I.q * gl, rec + gl * kRec);
-        }
-        const bool bad = (__ballot(bad_lane) & gmask) != 0ull;
-        const bool good = valid && !bad;
-        if (valid && gl == 0) I.bad[s] = bad ? 1 : 0;
-        lds_fence();
-        if (good && voigt) vamp::fill_dtab<kRec>(dtab, rec, K, gl, lanes);
-        lds_fence();
-        // 2. the item's pixels
-        if (good) {
-            const double ln_sd = free_sd ? log(sd) : 0.0;
-            double* out = I.ll + s;
-            for (int p = gl; p < I.np; p += lanes) {
-                const double xi = I.x[p];
-                double tau = 0.0;
-                for (int k = 0; k < K; ++k) tau += vamp::line_tau(voigt, xi, rec + k * kRec, dtab + k * vamp::DTAB_N);
-                const double sigma = free_sd ? sd : I.noise[p], ln_sigma = free_sd ? ln_sd : I.ln_noise[p];
-                const double r = (I.y[p] - exp(-tau)) / sigma;
-                out[(long long)p * I.S] = -0.5 * (r * r) - ln_sigma - HALF_LN_2PI;
-            }
-        }
-        lds_fence();                                   // the records are free for the next sample
-    }
-}
 
 // task: (item, first of kTile samples).  A tile is read along the pixels and written along the samples.
 __global__ __launch_bounds__(kTransBlock) void k_loo_transpose(const Matrix* __restrict__ mats, const int2* __restrict__ tasks) {
@@ -481,10 +405,10 @@ __global__ __launch_bounds__(kTotBlock) void k_loo_totals(const Totals* __restri
 }
 
 struct Pass {
-    size_t etask0 = 0, etask1 = 0;     // its k_loo_eval or k_loo_transpose workgroups
+    size_t etask0 = 0, etask1 = 0;     // its k_pointwise_ll or k_loo_transpose workgroups
     size_t ctask0 = 0, ctask1 = 0;     // its k_loo_column workgroups
     size_t range0 = 0, range1 = 0;     // its ranges of the plan
-    int region_doubles = 0;            // LDS of a wavefront of k_loo_eval
+    int region_doubles = 0;            // LDS of a wavefront of k_pointwise_ll
     long long used = 0;                // doubles of the scratch it fills
 };
 
@@ -591,18 +515,8 @@ VAMP_LOO_API int vamp_loo_pointwise(int device, void* hip_stream, int n_groups, 
     if (!err.empty()) return fail(err);
     const long long tot_pix = cg.tot_pix, tot_s = cg.tot_s;
     long long tot_noise = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        const std::string at = fn + "group " + std::to_string(g) + ": ";
-        if (!flux[g]) return fail(at + "NULL flux");
-        if (sample_sd[g] && noise[g]) return fail(at + "noise must be NULL when sample_sd is set: the chain's sd is the noise");
-        if (!sample_sd[g] && !noise[g]) return fail(at + "NULL noise without sample_sd");
-        for (int p = 0; p < n_pix[g]; ++p) {
-            if (!std::isfinite(flux[g][p])) return fail(at + "the flux is not finite at pixel " + std::to_string(p));
-            if (noise[g] && !(std::isfinite(noise[g][p]) && noise[g][p] > 0.0))
-                return fail(at + "the noise is not finite and positive at pixel " + std::to_string(p));
-        }
-        tot_noise += noise[g] ? n_pix[g] : 0;
-    }
+    const std::string data_err = check_chain_data(fn, n_groups, flux, noise, n_pix, sample_sd, tot_noise);
+    if (!data_err.empty()) return fail(data_err);
     if (tot_pix > (1LL << 30)) return fail(fn + "too many outputs");
     bool want_ll = false;
     for (int g = 0; ll && g < n_groups; ++g) want_ll |= ll[g] != nullptr;
@@ -621,27 +535,11 @@ VAMP_LOO_API int vamp_loo_pointwise(int device, void* hip_stream, int n_groups, 
     }
 
     // one buffer of doubles: abscissae | data | noise | ln noise
-    const long long o_x = 0, o_y = o_x + tot_pix, o_n = o_y + tot_pix, o_ln = o_n + tot_noise, o_end = o_ln + tot_noise;
-    std::vector<double> h_in((size_t)o_end);
-    {
-        long long op = 0, on = 0;
-        for (int g = 0; g < n_groups; ++g) {
-            for (int p = 0; p < n_pix[g]; ++p) {
-                h_in[o_x + op + p] = x[g][p];
-                h_in[o_y + op + p] = flux[g][p];
-                if (noise[g]) {
-                    h_in[o_n + on + p] = noise[g][p];
-                    h_in[o_ln + on + p] = std::log(noise[g][p]);
-                }
-            }
-            op += n_pix[g];
-            on += noise[g] ? n_pix[g] : 0;
-        }
-    }
+    DataOffsets in;
+    const std::vector<double> h_in = pack_chain_data(n_groups, x, flux, noise, n_pix, tot_pix, tot_noise, in);
     DevBuf d_in, d_bad, d_scratch;
     if (upload(d_in, h_in, st)) return -1;
     HIP_TRY(hipMalloc(&d_bad.p, (size_t)tot_s));
-    const double* dm = d_in.as<double>();
 
     const PassPlan plan = plan_passes(cg.cap, cg.S, n_pix, n_groups);
     HIP_TRY(hipMalloc(&d_scratch.p, (size_t)plan.scratch_len * sizeof(double)));
@@ -651,44 +549,18 @@ VAMP_LOO_API int vamp_loo_pointwise(int device, void* hip_stream, int n_groups, 
 
     std::vector<Item> items;
     std::vector<int2> etasks;
-    std::vector<long long> group_s_off(n_groups);
-    long long pix_off = 0, noise_off = 0, s_off = 0;     // of the range's group
-    for (const Range& r : plan.ranges) {
-        const int g = r.group, S = cg.S[g], K = n_comp[g], P = n_pix[g], p0 = r.p0, np = r.np;
-        const int lanes = vamp::group_lanes(kNarrow, P, K);
-        const int region = (64 / lanes) * slot_doubles(K);
-        Pass& ps = passes[r.pass];
-        if (r.offset == 0) ps.etask0 = etasks.size();
-        Item it;
-        it.chain = dbase[g];
-        it.x = dm + o_x + pix_off + p0;
-        it.y = dm + o_y + pix_off + p0;
-        it.noise = noise[g] ? dm + o_n + noise_off + p0 : nullptr;
-        it.ln_noise = noise[g] ? dm + o_ln + noise_off + p0 : nullptr;
-        it.ll = d_scratch.as<double>() + r.offset;
-        it.bad = d_bad.as<uint8_t>() + s_off;
-        it.ld = ld[g];
-        it.W = walkers[g]; it.D = cg.D[g]; it.K = K; it.q = mode[g] == 1 ? 4 : 3;
-        it.S = S; it.np = np; it.lanes = lanes;
-        const int ii = (int)items.size();
-        items.push_back(it);
-        for (int s0 = 0; s0 < S; s0 += kSamplesPerBlock) etasks.push_back(make_int2(ii, s0));
-        ps.region_doubles = region > ps.region_doubles ? region : ps.region_doubles;
-        ps.etask1 = etasks.size();
-        group_s_off[g] = s_off;
-        if (p0 + np == P) { pix_off += P; noise_off += noise[g] ? P : 0; s_off += S; }
-    }
+    build_eval(plan, cg, in, d_in.as<double>(), noise, n_pix, n_comp, mode, ld, walkers, dbase, kNarrow, d_scratch.as<double>(),
+               d_bad.as<uint8_t>(), items, etasks, passes);
     if (etasks.size() > 0x7fffffff) return fail(fn + "too many workgroups");
+    std::vector<long long> group_s_off(n_groups, 0);     // of a group's flags in d_bad
+    for (int g = 1; g < n_groups; ++g) group_s_off[g] = group_s_off[g - 1] + cg.S[g - 1];
 
     DevBuf d_items, d_etasks;
     if (upload(d_items, items, st) || upload(d_etasks, etasks, st)) return -1;
     std::vector<double> h_scratch;
     std::vector<uint8_t> h_bad;
     for (const Pass& ps : passes) {
-        hipLaunchKernelGGL(k_loo_eval, dim3((unsigned)(ps.etask1 - ps.etask0)), dim3(kEvalBlock),
-                           (size_t)kEvalWaves * ps.region_doubles * sizeof(double), st, d_items.as<Item>(),
-                           d_etasks.as<int2>() + ps.etask0, ps.region_doubles);
-        HIP_TRY(hipGetLastError());
+        if (launch_eval<true>(ps, d_items, d_etasks, st)) return -1;
         if (launch_columns(F, ps, st)) return -1;
         if (want_ll) {
             // the pass's scratch back before the next pass overwrites it; a bad sample's row was never written

@@ -2,11 +2,9 @@
 // (include/vamp_pred.h, libvamp_pred.so).  Definitions: DESIGN.md "Pointwise predictive density and WAIC".
 //
 // The work is a list of items (group, pixel range), packed greedily into passes whose log-likelihood scratch fits
-// scratch_bytes (chain_groups.hpp, which posterior.hip shares).  Two launches per pass, one at the end:
-//   k_pred_eval    one workgroup per (item, 64 samples).  A wavefront -- or, for short regions of few lines, a
-//                  16-lane group -- owns a sample: its parameters become line records and near-axis tables in LDS
-//                  once (lane_group.hpp), then its lanes walk the item's pixels and write the log-likelihood of the
-//                  pixel's datum, l_sp, to the scratch matrix.
+// scratch_bytes (chain_groups.hpp, which posterior.hip and loo.hip share).  Two launches per pass, one at the end:
+//   k_pointwise_ll the evaluation this library shares with loo.hip (pointwise_ll.hpp): one workgroup per (item, 64
+//                  samples) writes the log-likelihood of every pixel's datum, l_sp, to the scratch matrix.
 //   k_pred_column  one workgroup of 1024 threads per column (a pixel's l over the samples).  A thread holds its at
 //                  most 16 entries in registers; the maximum, the sum of exponentials, the sum and the centred sum of
 //                  squares are each a per-thread fold in sample order and a block reduction of fixed order, so a
@@ -24,6 +22,7 @@
 #include "../../include/vamp_pred.h"
 #include "chain_groups.hpp"
 #include "lane_group.hpp"
+#include "pointwise_ll.hpp"
 #include "side_call.hpp"
 #include "voigt_math.hpp"
 
@@ -46,39 +45,14 @@
 namespace {
 
 using namespace vamp::side;
-using vamp::lds_fence;
 
-constexpr int kEvalBlock = 256;            // four wavefronts
-constexpr int kEvalWaves = kEvalBlock / 64;
-constexpr int kSamplesPerBlock = 64;
-constexpr int kRec = 6;                    // doubles of a line record
 constexpr int kColBlock = 1024;            // one size for every column: the reduction order must not depend on the pass
 constexpr int kColPerThread = VAMP_PRED_MAX_SAMPLES / kColBlock;
 constexpr int kTotBlock = 64;
-constexpr double HALF_LN_2PI = 0.91893853320467274178;
 constexpr double kHighPwaic = 0.4;         // Vehtari, Gelman & Gabry (2017)
 
 static_assert(kColPerThread * kColBlock == VAMP_PRED_MAX_SAMPLES && kColPerThread <= 32, "a thread's entries are a bit mask");
-
-// LDS of one sample: line records and near-axis tables
-__host__ __device__ constexpr int slot_doubles(int K) { return K * (kRec + vamp::DTAB_N); }
-static_assert((size_t)kEvalWaves * slot_doubles(VAMP_PRED_MAX_COMPONENTS) * sizeof(double) <= 64 * 1024 &&
-                  (size_t)kEvalWaves * (64 / vamp::kNarrowLanes) * slot_doubles(vamp::kNarrowMaxK) * sizeof(double) <= 64 * 1024,
-              "a launch that asks for more than 64 KiB of LDS needs side::raise_lds_limit");
-
-struct Item {                      // one (group, pixel range)
-    const double* chain;           // the group's chain (device)
-    const double* x;               // the range's abscissa, data and, with known noise, noise and its logarithm (device)
-    const double* y;
-    const double* noise;           // NULL: the sample's sd
-    const double* ln_noise;
-    double* ll;                    // the item's scratch
-    uint8_t* bad;                  // the group's [S] flags
-    long long ld;                  // stride of t, in doubles
-    long long fs_s, fs_p;          // strides of the scratch
-    int W, D, K, q;                // q = 3 (Gauss) or 4 (Voigt) parameters per line
-    int S, np, lanes;              // lanes that own a sample (vamp::group_lanes)
-};
+static_assert(VAMP_PRED_MAX_COMPONENTS <= kEvalMaxComponents, "the evaluation's LDS is sized for kEvalMaxComponents lines");
 
 struct ColSet {                    // the columns of an item
     const double* src;             // l of (column c, sample s) = src[c * stride_c + s * stride_s]
@@ -97,60 +71,6 @@ struct Totals {                    // a group's per-pixel values and where its s
     const double* pwaic;
     int P;
 };
-
-__global__ __launch_bounds__(kEvalBlock) void k_pred_eval(const Item* __restrict__ items, const int2* __restrict__ tasks,
-                                                          int region_doubles) {
-    extern __shared__ double lds[];
-    const int2 task = tasks[blockIdx.x];
-    const Item I = items[task.x];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int lanes = I.lanes;
-    const vamp::LaneGroup lg = vamp::lane_group(lane, lanes);
-    const int nsub = lg.nsub, sub = lg.sub, gl = lg.gl;
-    const int K = I.K;
-    double* rec = lds + (size_t)wave * region_doubles + (size_t)sub * slot_doubles(K);
-    double* dtab = rec + K * kRec;
-    const int s_end = min(task.y + kSamplesPerBlock, I.S);
-    const bool voigt = I.q == 4, free_sd = I.noise == nullptr;
-    const unsigned long long gmask = vamp::group_mask(lanes, sub);
-
-    for (int sb = task.y + wave * nsub; sb < s_end; sb += kEvalWaves * nsub) {      // (uniform per wavefront)
-        const int s = sb + sub;
-        const bool valid = s < s_end;
-        // 1. the sample's line records and its sd, once
-        bool bad_lane = false;
-        double sd = 1.0;
-        if (valid) {
-            const int t = s / I.W, w = s - t * I.W;
-            const double* th = I.chain + (long long)t * I.ld + (long long)w * I.D;
-            if (free_sd) {
-                sd = th[I.D - 1];
-                bad_lane = !isfinite(sd) || sd <= 0.0;
-            }
-            if (gl < K) bad_lane |= vamp::line_record(voigt, th + I.q * gl, rec + gl * kRec);
-        }
-        const bool bad = (__ballot(bad_lane) & gmask) != 0ull;
-        const bool good = valid && !bad;
-        if (valid && gl == 0) I.bad[s] = bad ? 1 : 0;
-        lds_fence();
-        if (good && voigt) vamp::fill_dtab<kRec>(dtab, rec, K, gl, lanes);
-        lds_fence();
-        // 2. the item's pixels
-        if (good) {
-            const double ln_sd = free_sd ? log(sd) : 0.0;
-            double* out = I.ll + (long long)s * I.fs_s;
-            for (int p = gl; p < I.np; p += lanes) {
-                const double xi = I.x[p];
-                double tau = 0.0;
-                for (int k = 0; k < K; ++k) tau += vamp::line_tau(voigt, xi, rec + k * kRec, dtab + k * vamp::DTAB_N);
-                const double sigma = free_sd ? sd : I.noise[p], ln_sigma = free_sd ? ln_sd : I.ln_noise[p];
-                const double r = (I.y[p] - exp(-tau)) / sigma;
-                out[(long long)p * I.fs_p] = -0.5 * (r * r) - ln_sigma - HALF_LN_2PI;
-            }
-        }
-        lds_fence();                                   // the records are free for the next sample
-    }
-}
 
 __global__ __launch_bounds__(kColBlock) void k_pred_column(const ColSet* __restrict__ sets, const int2* __restrict__ tasks) {
     __shared__ double red[kColBlock];
@@ -234,9 +154,9 @@ __global__ __launch_bounds__(kTotBlock) void k_pred_totals(const Totals* __restr
 }
 
 struct Pass {
-    size_t etask0, etask1;         // its k_pred_eval workgroups
+    size_t etask0, etask1;         // its k_pointwise_ll workgroups
     size_t ctask0, ctask1;         // its k_pred_column workgroups
-    int region_doubles = 0;        // LDS of a wavefront of k_pred_eval
+    int region_doubles = 0;        // LDS of a wavefront of k_pointwise_ll
 };
 
 }  // namespace
@@ -263,18 +183,8 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
     if (!err.empty()) return fail(err);
     const long long tot_pix = cg.tot_pix, tot_s = cg.tot_s;
     long long tot_noise = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        const std::string at = fn + "group " + std::to_string(g) + ": ";
-        if (!flux[g]) return fail(at + "NULL flux");
-        if (sample_sd[g] && noise[g]) return fail(at + "noise must be NULL when sample_sd is set: the chain's sd is the noise");
-        if (!sample_sd[g] && !noise[g]) return fail(at + "NULL noise without sample_sd");
-        for (int p = 0; p < n_pix[g]; ++p) {
-            if (!std::isfinite(flux[g][p])) return fail(at + "the flux is not finite at pixel " + std::to_string(p));
-            if (noise[g] && !(std::isfinite(noise[g][p]) && noise[g][p] > 0.0))
-                return fail(at + "the noise is not finite and positive at pixel " + std::to_string(p));
-        }
-        tot_noise += noise[g] ? n_pix[g] : 0;
-    }
+    const std::string data_err = check_chain_data(fn, n_groups, flux, noise, n_pix, sample_sd, tot_noise);
+    if (!data_err.empty()) return fail(data_err);
     if (tot_pix > (1LL << 30)) return fail(fn + "too many outputs");
 
     DeviceRestore restore;
@@ -291,24 +201,9 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
     }
 
     // one buffer of doubles: abscissae | data | noise | ln noise | per-pixel outputs | group outputs
-    const long long o_x = 0, o_y = o_x + tot_pix, o_n = o_y + tot_pix, o_ln = o_n + tot_noise, o_lppd = o_ln + tot_noise,
-                    o_lm = o_lppd + tot_pix, o_pw = o_lm + tot_pix, o_grp = o_pw + tot_pix, o_end = o_grp + 4ll * n_groups;
-    std::vector<double> h_in((size_t)o_lppd);
-    {
-        long long op = 0, on = 0;
-        for (int g = 0; g < n_groups; ++g) {
-            for (int p = 0; p < n_pix[g]; ++p) {
-                h_in[o_x + op + p] = x[g][p];
-                h_in[o_y + op + p] = flux[g][p];
-                if (noise[g]) {
-                    h_in[o_n + on + p] = noise[g][p];
-                    h_in[o_ln + on + p] = std::log(noise[g][p]);
-                }
-            }
-            op += n_pix[g];
-            on += noise[g] ? n_pix[g] : 0;
-        }
-    }
+    DataOffsets in;
+    const std::vector<double> h_in = pack_chain_data(n_groups, x, flux, noise, n_pix, tot_pix, tot_noise, in);
+    const long long o_lppd = in.end, o_lm = o_lppd + tot_pix, o_pw = o_lm + tot_pix, o_grp = o_pw + tot_pix, o_end = o_grp + 4ll * n_groups;
     DevBuf d_main, d_bad, d_counts, d_scratch;
     HIP_TRY(hipMalloc(&d_main.p, (size_t)o_end * sizeof(double)));
     HIP_TRY(hipMalloc(&d_bad.p, (size_t)tot_s));
@@ -316,54 +211,41 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
     HIP_TRY(hipMemcpyAsync(d_main.p, h_in.data(), h_in.size() * sizeof(double), hipMemcpyHostToDevice, st));
     double* dm = d_main.as<double>();
 
-    // the plan (chain_groups.hpp): one item and one column set per range, a group's totals after its last range
+    // the plan (chain_groups.hpp): one item (pointwise_ll.hpp) and one column set per range, a group's totals after
+    // its last range
     const PassPlan plan = plan_passes(cg.cap, cg.S, n_pix, n_groups);
-    const long long scratch_len = plan.scratch_len;
-    HIP_TRY(hipMalloc(&d_scratch.p, (size_t)scratch_len * sizeof(double)));
+    HIP_TRY(hipMalloc(&d_scratch.p, (size_t)plan.scratch_len * sizeof(double)));
     std::vector<Item> items;
     std::vector<ColSet> sets;
     std::vector<Totals> totals;
     std::vector<int2> etasks, ctasks;
     std::vector<Pass> passes(plan.first.size());
-    long long pix_off = 0, noise_off = 0, s_off = 0;     // of the range's group
+    build_eval(plan, cg, in, dm, noise, n_pix, n_comp, mode, ld, walkers, dbase, VAMP_PRED_NARROW != 0, d_scratch.as<double>(),
+               d_bad.as<uint8_t>(), items, etasks, passes);
+    long long pix_off = 0, s_off = 0;                    // of the range's group
     for (const Range& r : plan.ranges) {
-        const int g = r.group, S = cg.S[g], K = n_comp[g], P = n_pix[g], p0 = r.p0, np = r.np;
-        const int lanes = vamp::group_lanes(VAMP_PRED_NARROW, P, K);
-        const int region = (64 / lanes) * slot_doubles(K);
+        const int g = r.group, S = cg.S[g], P = n_pix[g], p0 = r.p0, np = r.np;
         Pass& ps = passes[r.pass];
-        if (r.offset == 0) { ps.etask0 = etasks.size(); ps.ctask0 = ctasks.size(); }
-        Item it;
-        it.chain = dbase[g];
-        it.x = dm + o_x + pix_off + p0;
-        it.y = dm + o_y + pix_off + p0;
-        it.noise = noise[g] ? dm + o_n + noise_off + p0 : nullptr;
-        it.ln_noise = noise[g] ? dm + o_ln + noise_off + p0 : nullptr;
-        it.ll = d_scratch.as<double>() + r.offset;
-        it.bad = d_bad.as<uint8_t>() + s_off;
-        it.ld = ld[g];
-        it.fs_s = VAMP_PRED_PIXEL_MAJOR ? 1 : np;
-        it.fs_p = VAMP_PRED_PIXEL_MAJOR ? S : 1;
-        it.W = walkers[g]; it.D = cg.D[g]; it.K = K; it.q = mode[g] == 1 ? 4 : 3;
-        it.S = S; it.np = np; it.lanes = lanes;
+        if (r.offset == 0) ps.ctask0 = ctasks.size();
         ColSet cs;
-        cs.src = it.ll; cs.bad = it.bad;
+        cs.src = d_scratch.as<double>() + r.offset;
+        cs.bad = d_bad.as<uint8_t>() + s_off;
         cs.lppd = dm + o_lppd + pix_off + p0;
         cs.ll_mean = dm + o_lm + pix_off + p0;
         cs.pwaic = dm + o_pw + pix_off + p0;
         cs.counts = p0 == 0 ? d_counts.as<int32_t>() + 2 * g : nullptr;
-        cs.stride_c = it.fs_p; cs.stride_s = it.fs_s; cs.S = S;
-        const int ii = (int)items.size();
-        items.push_back(it);
+        cs.stride_c = VAMP_PRED_PIXEL_MAJOR ? S : 1;
+        cs.stride_s = VAMP_PRED_PIXEL_MAJOR ? 1 : np;
+        cs.S = S;
+        const int ii = (int)sets.size();
         sets.push_back(cs);
-        for (int s0 = 0; s0 < S; s0 += kSamplesPerBlock) etasks.push_back(make_int2(ii, s0));
         for (int c = 0; c < np; ++c) ctasks.push_back(make_int2(ii, c));
-        ps.region_doubles = region > ps.region_doubles ? region : ps.region_doubles;
-        ps.etask1 = etasks.size(); ps.ctask1 = ctasks.size();
+        ps.ctask1 = ctasks.size();
         if (p0 + np == P) {
             Totals t;
             t.lppd = dm + o_lppd + pix_off; t.ll_mean = dm + o_lm + pix_off; t.pwaic = dm + o_pw + pix_off; t.P = P;
             totals.push_back(t);
-            pix_off += P; noise_off += noise[g] ? P : 0; s_off += S;
+            pix_off += P; s_off += S;
         }
     }
     if (etasks.size() > 0x7fffffff || ctasks.size() > 0x7fffffff) return fail(fn + "too many workgroups");
@@ -373,10 +255,7 @@ VAMP_PRED_API int vamp_pred_pointwise(int device, void* hip_stream, int n_groups
         upload(d_ctasks, ctasks, st))
         return -1;
     for (const Pass& ps : passes) {
-        hipLaunchKernelGGL(k_pred_eval, dim3((unsigned)(ps.etask1 - ps.etask0)), dim3(kEvalBlock),
-                           (size_t)kEvalWaves * ps.region_doubles * sizeof(double), st, d_items.as<Item>(),
-                           d_etasks.as<int2>() + ps.etask0, ps.region_doubles);
-        HIP_TRY(hipGetLastError());
+        if (launch_eval<VAMP_PRED_PIXEL_MAJOR != 0>(ps, d_items, d_etasks, st)) return -1;
         hipLaunchKernelGGL(k_pred_column, dim3((unsigned)(ps.ctask1 - ps.ctask0)), dim3(kColBlock), 0, st, d_sets.as<ColSet>(),
                            d_ctasks.as<int2>() + ps.ctask0);
         HIP_TRY(hipGetLastError());

@@ -1,6 +1,7 @@
 // side_call.hpp -- the frame of an entry point of a side library (chain_diag.hip, posterior.hip, evidence.hip,
-// predictive.hip): the error slot, buffers and the caller's device released on every exit path, device selection, the
-// dynamic-LDS limit, staging of host chains, result copies.  DESIGN.md "The call frame of the side libraries".
+// predictive.hip, loo.hip, relabel.hip, fisher.hip): the error slot, buffers and the caller's device released on every
+// exit path, device selection, the dynamic-LDS limit, staging of host chains, result copies.  DESIGN.md "The call frame
+// of the side libraries".
 //
 // Host code only.  Each library is one translation unit built with -fvisibility=hidden, so each holds its own copy
 // of the state below (the error slot, the record of raised limits).  The argument checks, their messages and

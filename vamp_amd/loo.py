@@ -20,8 +20,8 @@ import ctypes as C
 import numpy as np
 
 from . import _loo_lib
-from ._sidelib import (MAX_CHAIN_SAMPLES as MAX_SAMPLES, chain_args, check_chain_shapes, context_layout, fits_with_chain, host_layout,
-                       per_group, time_step)
+from ._sidelib import (MAX_CHAIN_SAMPLES as MAX_SAMPLES, chain_args, context_records, data_args, fits_records, host_layout, outputs,
+                       pointer_array, pointwise_records, split_records, time_step)
 
 HIGH_KHAT = 0.7               # a pixel's PSIS-LOO is not to be trusted past this khat (Vehtari, Gelman & Gabry 2017)
 
@@ -54,15 +54,6 @@ class LooRecord:
                 f"n_high_k={self.n_high_k}, n_used={self.n_used}, n_bad={self.n_bad}, step={self.step})")
 
 
-def _outputs(G, tot_pix, want):
-    out = {k: np.empty(tot_pix) for k in _PIX if k in want}
-    out.update({k: np.empty(G) for k in _GRP if k in want})
-    out.update({k: np.empty(G, dtype=np.int32) for k in _CNT if k in want})
-    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-    arg = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else None
-    return out, [arg(k, dp) for k in _PIX + _GRP] + [arg(k, ip) for k in _CNT]
-
-
 def _call(device, xs, fluxes, noises, n_comp, modes, sample_sd, bases, is_device, ld, n_keep, walkers, scratch_bytes=0, stream=None,
           want=_FLAT):
     """One vamp_loo_pointwise call; returns the flat output arrays by name (group order).  ``want``: the outputs asked
@@ -70,21 +61,15 @@ def _call(device, xs, fluxes, noises, n_comp, modes, sample_sd, bases, is_device
     log-likelihood matrix the call used (rows of bad samples NaN)."""
     lib = _loo_lib.load()
     G = len(bases)
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-    xs, fluxes = [f64(x) for x in xs], [f64(f) for f in fluxes]
-    noises = [None if n is None else f64(n) for n in noises]
-    for x, f, n in zip(xs, fluxes, noises):
-        if f.shape != x.shape or (n is not None and n.shape != x.shape):
-            raise ValueError("flux and noise must have the abscissa's shape")
-    out, args = _outputs(G, int(sum(x.size for x in xs)), want)
-    ptrs = lambda arrays: (C.c_void_p * G)(*[None if a is None else a.ctypes.data for a in arrays])
+    xs, fluxes, noises = data_args(xs, fluxes, noises)
+    out, args = outputs(G, int(sum(x.size for x in xs)), want, _PIX, _GRP, _CNT)
     ll = None
     if "ll" in want:
         ll = [np.empty((int(n) * int(w), x.size)) for n, w, x in zip(n_keep, walkers, xs)]
     _loo_lib.check(lib.vamp_loo_pointwise(
-        int(device), C.c_void_p(stream or 0), G, ptrs(xs), ptrs(fluxes), ptrs(noises),
+        int(device), C.c_void_p(stream or 0), G, pointer_array(xs), pointer_array(fluxes), pointer_array(noises),
         *chain_args([x.size for x in xs], n_comp, modes, sample_sd, bases, is_device, ld, n_keep, walkers), int(scratch_bytes),
-        *args, None if ll is None else ptrs(ll)), lib)
+        *args, None if ll is None else pointer_array(ll)), lib)
     if ll is not None:
         out["ll"] = ll
     return out
@@ -96,7 +81,7 @@ def _call_loglik(device, lls, n_samples, n_pix, skips=None, is_device=False, scr
     lib = _loo_lib.load()
     G = len(lls)
     i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
-    out, args = _outputs(G, int(sum(int(p) for p in n_pix)), want)
+    out, args = outputs(G, int(sum(int(p) for p in n_pix)), want, _PIX, _GRP, _CNT)
     skip_arg = None
     if skips is not None:
         skips = [None if s is None else np.ascontiguousarray(s, dtype=np.uint8) for s in skips]
@@ -117,49 +102,21 @@ def _loo_host(xs, fluxes, noises, arrays, n_comp, modes, steps, device, scratch_
 
 
 def _split(flat, n_pix, steps):
-    out, op = [], 0
-    for g, (P, st) in enumerate(zip(n_pix, steps)):
-        out.append(LooRecord(st, **{k: flat[k][op:op + P].copy() for k in _PIX}, **{k: float(flat[k][g]) for k in _GRP},
-                             **{k: int(flat[k][g]) for k in _CNT}))
-        op += P
-    return out
+    return split_records(LooRecord, flat, n_pix, steps, _PIX, _GRP, _CNT)
 
 
 def pointwise_loo(xs, fluxes, noises, chains, n_comp, mode, device=0, scratch_bytes=0, steps=1):
     """Records of one host [N, W, D] chain on the abscissa ``xs`` with the data ``fluxes`` and the noise ``noises``
     (returns one ``LooRecord``) or of a list of chains on lists of those (returns a list), all in one library call.
     The arguments are those of ``predictive.pointwise_predictive``."""
-    single = isinstance(chains, np.ndarray)
-    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in ([chains] if single else chains)]
-    xs, fluxes, noises = ([v] if single else list(v) for v in (xs, fluxes, noises))
-    if not len(xs) == len(fluxes) == len(noises) == len(arrays):
-        raise ValueError("one abscissa, one flux and one noise (or None) per chain are required")
-    G = len(arrays)
-    if G == 0:
-        return []
-    n_comp, modes, steps = per_group(n_comp, G, int), per_group(mode, G, int), per_group(steps, G, int)
-    check_chain_shapes(arrays, n_comp, modes, [int(n is None) for n in noises], [f"free sd = {n is None}" for n in noises])
-    flat = _loo_host(xs, fluxes, noises, arrays, n_comp, modes, steps, int(device), int(scratch_bytes))
-    res = _split(flat, [len(x) for x in xs], steps)
-    return res[0] if single else res
+    return pointwise_records(_loo_host, _split, xs, fluxes, noises, chains, n_comp, mode, device, scratch_bytes, steps)
 
 
 def context_loo(ctx, chain_ptr, n_keep, xs, fluxes, noises, scratch_bytes=0):
     """Records of every region of the DEVICE chain ``HipContext.run_dev`` wrote at ``chain_ptr`` ([n_keep, total_theta]
     fp64), read in place, one record per region, from one library call on the context's device (default stream, after
     the context's stream is synchronised).  The arguments are those of ``predictive.context_predictive``."""
-    ctx.synchronize()                  # the sampler's stream is done with the chain before the default stream reads it
-    if isinstance(xs, np.ndarray) and xs.ndim == 1:
-        xs, fluxes, noises = [xs], [fluxes], [noises]
-    R = len(ctx.ndims)
-    if not len(xs) == len(fluxes) == len(noises) == R:
-        raise ValueError("one abscissa, one flux and one noise (or None) per region of the context are required")
-    ks, modes, sds, bases, ld, n_keep, walkers = context_layout(ctx, chain_ptr, n_keep)
-    for sd, n in zip(sds, noises):
-        if bool(sd) != (n is None):
-            raise ValueError("a region's noise is None exactly when the context samples its sd")
-    flat = _call(ctx.device, xs, fluxes, noises, ks, modes, sds, bases, True, ld, n_keep, walkers, scratch_bytes)
-    return _split(flat, [len(x) for x in xs], [1] * R)
+    return context_records(_call, _split, ctx, chain_ptr, n_keep, xs, fluxes, noises, scratch_bytes)
 
 
 def fits_loo(fits, device=0, scratch_bytes=0):
@@ -167,16 +124,7 @@ def fits_loo(fits, device=0, scratch_bytes=0):
     fit's ``mcmc.loo()`` cache is filled from it.  A chain of more than MAX_SAMPLES samples is read at the smallest
     time step that fits; the step is each record's ``step``.  Fits without a chain are left out.  Returns (fits
     scored, their records)."""
-    have = fits_with_chain(fits)
-    if not have:
-        return [], []
-    steps = [time_step(f._chain_dev.shape[0], f._chain_dev.shape[1]) for f in have]
-    recs = pointwise_loo([f._x for f in have], [f._flux for f in have], [None if f._sample_sd else f.noise for f in have],
-                         [f._chain_dev for f in have], [f._n for f in have], [int(f._mode) for f in have], device=device,
-                         scratch_bytes=scratch_bytes, steps=steps)
-    for f, r in zip(have, recs):
-        f.mcmc._set_loo(r)
-    return have, recs
+    return fits_records(pointwise_loo, "_set_loo", fits, device, scratch_bytes)
 
 
 def loo_from_loglik(ll, skip=None, device=0, scratch_bytes=0):

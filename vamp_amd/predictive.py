@@ -18,8 +18,8 @@ import ctypes as C
 import numpy as np
 
 from . import _pred_lib
-from ._sidelib import (MAX_CHAIN_SAMPLES as MAX_SAMPLES, chain_args, check_chain_shapes, context_layout, fits_with_chain, host_layout,
-                       per_group, time_step)
+from ._sidelib import (MAX_CHAIN_SAMPLES as MAX_SAMPLES, chain_args, context_records, data_args, fits_records, host_layout, outputs,
+                       pointer_array, pointwise_records, split_records, time_step)
 
 HIGH_P_WAIC = 0.4             # a pixel's WAIC is not to be trusted past this p_waic (Vehtari, Gelman & Gabry 2017)
 
@@ -66,23 +66,11 @@ def _call(device, xs, fluxes, noises, n_comp, modes, sample_sd, bases, is_device
     for (the others are passed as NULL)."""
     lib = _pred_lib.load()
     G = len(bases)
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-    xs, fluxes = [f64(x) for x in xs], [f64(f) for f in fluxes]
-    noises = [None if n is None else f64(n) for n in noises]
-    for x, f, n in zip(xs, fluxes, noises):
-        if f.shape != x.shape or (n is not None and n.shape != x.shape):
-            raise ValueError("flux and noise must have the abscissa's shape")
-    tp = int(sum(x.size for x in xs))
-    out = {k: np.empty(tp) for k in _PIX if k in want}
-    out.update({k: np.empty(G) for k in _GRP if k in want})
-    out.update({k: np.empty(G, dtype=np.int32) for k in _CNT if k in want})
-    ptrs = lambda arrays: (C.c_void_p * G)(*[None if a is None else a.ctypes.data for a in arrays])
-    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-    arg = lambda k, ty: out[k].ctypes.data_as(ty) if k in out else None
+    xs, fluxes, noises = data_args(xs, fluxes, noises)
+    out, args = outputs(G, int(sum(x.size for x in xs)), want, _PIX, _GRP, _CNT)
     _pred_lib.check(lib.vamp_pred_pointwise(
-        int(device), C.c_void_p(stream or 0), G, ptrs(xs), ptrs(fluxes), ptrs(noises),
-        *chain_args([x.size for x in xs], n_comp, modes, sample_sd, bases, is_device, ld, n_keep, walkers), int(scratch_bytes),
-        *[arg(k, dp) for k in _PIX + _GRP], *[arg(k, ip) for k in _CNT]), lib)
+        int(device), C.c_void_p(stream or 0), G, pointer_array(xs), pointer_array(fluxes), pointer_array(noises),
+        *chain_args([x.size for x in xs], n_comp, modes, sample_sd, bases, is_device, ld, n_keep, walkers), int(scratch_bytes), *args), lib)
     return out
 
 
@@ -94,12 +82,7 @@ def _pred_host(xs, fluxes, noises, arrays, n_comp, modes, steps, device, scratch
 
 
 def _split(flat, n_pix, steps):
-    out, op = [], 0
-    for g, (P, st) in enumerate(zip(n_pix, steps)):
-        out.append(PredictiveRecord(st, **{k: flat[k][op:op + P].copy() for k in _PIX}, **{k: float(flat[k][g]) for k in _GRP},
-                                    **{k: int(flat[k][g]) for k in _CNT}))
-        op += P
-    return out
+    return split_records(PredictiveRecord, flat, n_pix, steps, _PIX, _GRP, _CNT)
 
 
 def pointwise_predictive(xs, fluxes, noises, chains, n_comp, mode, device=0, scratch_bytes=0, steps=1):
@@ -108,19 +91,7 @@ def pointwise_predictive(xs, fluxes, noises, chains, n_comp, mode, device=0, scr
     A noise of ``None`` means free sd: the chain's last dimension.  ``n_comp``, ``mode`` (0 = Gauss: (A, c, sigma) per
     line, 1 = Voigt: (A, c, L_fwhm, G_fwhm)) and ``steps`` (read every n-th kept sample) are one value for all, or one
     per chain."""
-    single = isinstance(chains, np.ndarray)
-    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in ([chains] if single else chains)]
-    xs, fluxes, noises = ([v] if single else list(v) for v in (xs, fluxes, noises))
-    if not len(xs) == len(fluxes) == len(noises) == len(arrays):
-        raise ValueError("one abscissa, one flux and one noise (or None) per chain are required")
-    G = len(arrays)
-    if G == 0:
-        return []
-    n_comp, modes, steps = per_group(n_comp, G, int), per_group(mode, G, int), per_group(steps, G, int)
-    check_chain_shapes(arrays, n_comp, modes, [int(n is None) for n in noises], [f"free sd = {n is None}" for n in noises])
-    flat = _pred_host(xs, fluxes, noises, arrays, n_comp, modes, steps, int(device), int(scratch_bytes))
-    res = _split(flat, [len(x) for x in xs], steps)
-    return res[0] if single else res
+    return pointwise_records(_pred_host, _split, xs, fluxes, noises, chains, n_comp, mode, device, scratch_bytes, steps)
 
 
 def context_predictive(ctx, chain_ptr, n_keep, xs, fluxes, noises, scratch_bytes=0):
@@ -128,18 +99,7 @@ def context_predictive(ctx, chain_ptr, n_keep, xs, fluxes, noises, scratch_bytes
     fp64, e.g. ``tensor.data_ptr()``), read in place, one record per region, from one library call on the context's
     device (default stream, after the context's stream is synchronised).  ``xs``, ``fluxes``, ``noises``: the regions'
     abscissae and data as they were given to ``set_regions``; a region with free sd has the noise ``None``."""
-    ctx.synchronize()                  # the sampler's stream is done with the chain before the default stream reads it
-    if isinstance(xs, np.ndarray) and xs.ndim == 1:
-        xs, fluxes, noises = [xs], [fluxes], [noises]
-    R = len(ctx.ndims)
-    if not len(xs) == len(fluxes) == len(noises) == R:
-        raise ValueError("one abscissa, one flux and one noise (or None) per region of the context are required")
-    ks, modes, sds, bases, ld, n_keep, walkers = context_layout(ctx, chain_ptr, n_keep)
-    for sd, n in zip(sds, noises):
-        if bool(sd) != (n is None):
-            raise ValueError("a region's noise is None exactly when the context samples its sd")
-    flat = _call(ctx.device, xs, fluxes, noises, ks, modes, sds, bases, True, ld, n_keep, walkers, scratch_bytes)
-    return _split(flat, [len(x) for x in xs], [1] * R)
+    return context_records(_call, _split, ctx, chain_ptr, n_keep, xs, fluxes, noises, scratch_bytes)
 
 
 def fits_predictive(fits, device=0, scratch_bytes=0):
@@ -148,13 +108,4 @@ def fits_predictive(fits, device=0, scratch_bytes=0):
     ``mcmc.waic()`` cache is filled from it.  A chain of more than MAX_SAMPLES samples is read at the smallest time
     step that fits; the step is each record's ``step``.  Fits without a chain are left out.  Returns (fits scored,
     their records)."""
-    have = fits_with_chain(fits)
-    if not have:
-        return [], []
-    steps = [time_step(f._chain_dev.shape[0], f._chain_dev.shape[1]) for f in have]
-    recs = pointwise_predictive([f._x for f in have], [f._flux for f in have], [None if f._sample_sd else f.noise for f in have],
-                                [f._chain_dev for f in have], [f._n for f in have], [int(f._mode) for f in have], device=device,
-                                scratch_bytes=scratch_bytes, steps=steps)
-    for f, r in zip(have, recs):
-        f.mcmc._set_predictive(r)
-    return have, recs
+    return fits_records(pointwise_predictive, "_set_predictive", fits, device, scratch_bytes)
