@@ -10,7 +10,9 @@ only moves data -- the relabelled chain, in place against out of place, host aga
 caller's stream, every output alone -- is compared bit for bit.  The moments (label_mean, label_sd, scale_used) are
 compared at 1e-12 of the largest |value| of their parameter, against the restatement's moments under the kernel's own
 permutations.  tests/test_relabel.py shows that a row-greedy assignment misses the optimality bar by nine orders of
-magnitude and more, so these comparisons would see it.  Every case prints its worst error / bar
+magnitude and more, so these comparisons would see it.  Every round of the iteration is held to relabel_ref.check_rounds
+(chained one-round calls against one call of R rounds, the descent of J, the fixed point), which tests/test_relabel.py shows
+to fail on five planted errors of the host loop.  Every case prints its worst error / bar
 (profiles/relabel_limits.txt)."""
 import numpy as np
 import pytest
@@ -20,7 +22,7 @@ import relabel_ref as ref
 
 pytestmark = pytest.mark.gpu
 
-FLAT = ("perm", "cost", "label_mean", "label_sd", "scale", "n_iter", "n_changed", "n_switched", "n_used", "n_bad")
+FLAT = ref.FLAT
 
 
 def _report(label, worst, extra=""):
@@ -110,18 +112,7 @@ def test_solver_on_finite_matrices_whose_potentials_overflow(K):
 
 
 # ---- 2. chains against the restatement -----------------------------------------------------------------------------
-def _group(th, W, K, mode, sd, reference, scale=None, pad=0):
-    """a chain [n_keep, W, D] from [S, D] samples inside a buffer whose rows are W D + pad doubles apart"""
-    S, D = th.shape
-    assert S % W == 0 and D == ref.Q_OF_MODE[mode] * K + sd
-    buf = np.full((S // W, W * D + pad), -777.0)
-    buf[:, :W * D] = th.reshape(S // W, W * D)
-    return {"buf": buf, "W": W, "D": D, "K": K, "mode": mode, "sd": sd, "ref": np.asarray(reference, dtype=np.float64), "scale": scale,
-            "n_keep": S // W}
-
-
-def _samples(g):
-    return g["buf"][:, :g["W"] * g["D"]].reshape(-1, g["D"])
+_group, _samples = ref.group, ref.samples          # shared with the CPU tests of the rounds checker (tests/relabel_ref.py)
 
 
 def _run(groups, max_iter=1, out="apart", want=FLAT, device=False, stream=None):
@@ -153,75 +144,7 @@ def _run(groups, max_iter=1, out="apart", want=FLAT, device=False, stream=None):
             for i in range(len(groups))]
 
 
-def _moment_bar(v):
-    """1e-12 of the largest |value| of every parameter type [q]"""
-    return 1e-12 * np.maximum(np.abs(v).reshape(-1, v.shape[-1]).max(axis=0), 1e-300)
-
-
-def _check(got, g, label, max_iter=1, exact=True):
-    """one group's outputs at max_iter = 1 against the restatement; returns the worst error / bar"""
-    K, q, sd, W, D = g["K"], ref.Q_OF_MODE[g["mode"]], g["sd"], g["W"], g["D"]
-    th = _samples(g)
-    S = th.shape[0]
-    want = ref.relabel(th, K, g["mode"], sd, g["ref"], g["scale"], max_iter)
-    good = want["good"]
-    bad = np.setdiff1d(np.arange(S), good)
-    perm = got["perm"].astype(np.int64)
-    assert perm.shape == (S, K) and got["cost"].shape == (S,)
-    assert (got["n_used"], got["n_bad"]) == (want["n_used"], want["n_bad"]) == (len(good), len(bad)), label
-    assert np.array_equal(perm[bad], np.tile(np.arange(K), (len(bad), 1))) and np.isnan(got["cost"][bad]).all(), label
-    assert np.array_equal(np.sort(perm, axis=1), np.tile(np.arange(K), (S, 1))), label
-    worst = 0.0
-    v = ref.lines(th, K, q)[good]
-    # the scale first: the costs below are the restatement's under the scale the KERNEL used
-    if len(good):
-        sb = 1e-12 * np.maximum(1.0, np.abs(want["scale"]))
-        assert np.all(np.abs(got["scale"] - want["scale"]) <= sb), (label, got["scale"], want["scale"])
-        worst = max(worst, float(np.max(np.abs(got["scale"] - want["scale"]) / sb)))
-    if g["scale"] is not None:
-        assert np.array_equal(got["scale"], g["scale"])
-    if max_iter == 1 and len(good):
-        C_ = ref.cost_matrices(v, g["ref"].reshape(K, q), got["scale"])
-        assert np.isfinite(C_).all()
-        _, opt = ref.assign(C_)
-        mine = ref.perm_cost(C_, perm[good])
-        B = ref.bar(C_)
-        if K == 1:      # no solver: the returned cost is one entry of the matrix, which is the restatement's bit for bit
-            assert np.array_equal(got["cost"][good], C_[:, 0, 0]), label
-        assert np.all(mine <= opt + B), (label, float(np.max((mine - opt) / B)))
-        assert np.all(np.abs(got["cost"][good] - mine) <= B), (label, float(np.max(np.abs(got["cost"][good] - mine) / B)))
-        worst = max(worst, float(np.max(np.maximum(mine - opt, np.abs(got["cost"][good] - mine)) / np.maximum(B, 1e-300))))
-        if 1 < K <= ref.BRUTE_MAX_K and exact:
-            pb, _, gap = ref.assign_brute(C_)
-            clear = gap > 2 * B
-            assert (~clear).mean() <= 0.01 and np.array_equal(perm[good][clear], pb[clear]), label
-        ident = np.arange(K)
-        assert got["n_switched"] == int((perm[good] != ident).any(axis=1).sum()) == got["n_changed"] and got["n_iter"] == 1, label
-    # data movement, bit for bit
-    if got.get("out") is not None:
-        moved = ref.gather(th, perm, K, q)
-        out = got["out"]
-        assert np.array_equal(out[:, :W * D].reshape(S, D), moved, equal_nan=True), label
-        pad = out[:, W * D:]
-        assert np.all(pad == (-777.0 if got["input"] is None else -555.0)), label                  # the padding comes back untouched
-        if got["input"] is not None:
-            assert np.array_equal(got["input"], g["buf"], equal_nan=True), label                   # and out of place the input
-    # the moments under the kernel's own permutations
-    moved = np.take_along_axis(v, perm[good][:, :, None], axis=1)
-    if len(good) >= 1:
-        mb = _moment_bar(v)
-        err = np.abs(got["label_mean"] - moved.mean(axis=0)) / mb
-        assert np.all(err <= 1.0), (label, err.max())
-        worst = max(worst, float(err.max()))
-    else:
-        assert np.isnan(got["label_mean"]).all() and np.isnan(got["label_sd"]).all()
-    if len(good) >= 2:
-        err = np.abs(got["label_sd"] - moved.std(axis=0, ddof=1)) / _moment_bar(v)
-        assert np.all(err <= 1.0), (label, err.max())
-        worst = max(worst, float(err.max()))
-    elif len(good) == 1:
-        assert np.isnan(got["label_sd"]).all()
-    return worst
+_moment_bar, _check = ref.moment_bar, ref.check_round
 
 
 SHAPES = (7, 8, 9, 63, 64, 65, 129)
@@ -432,6 +355,98 @@ def test_rounds_on_a_two_line_chain_with_walkers_swapped_at_random():
     two = _run([g], max_iter=2)[0]
     assert two["n_iter"] == 2 and (two["n_changed"] == 0) == (want["n_iter"] == 2)
     _report("rounds: two-line chain, %d of 16 walkers swapped, n_iter %d" % (swapped.sum(), got["n_iter"]), worst)
+
+
+def _rounds_extra(res):
+    return ", stop %s, J %.6g -> %.6g in %d rounds" % (res["stop"], res["J"][0], res["J"][-1], len(res["J"]))
+
+
+@pytest.mark.parametrize("given", [True, False], ids=["given", "pooled"])
+@pytest.mark.parametrize("case", ref.ROUNDS_CASES, ids=lambda c: "K%d-q%d-sd%d-sep%g" % c[:4])
+def test_every_round_on_crowded_chains(case, given):
+    """relabel_ref.check_rounds on the library: chained one-round calls against one R-round call for every R <= R_MAX bit
+    for bit, n_iter, n_changed and converged, every round to the solver's bar, the descent of J and the fixed point;
+    host chains out of place, and the cases with padded rows (one per lane width) in place on device chains as well"""
+    g, label = ref.rounds_case(case, given), ref.rounds_label(case, given)
+    res = ref.check_rounds(lambda groups, R: _run(groups, max_iter=R), g, label, ref.R_MAX)
+    _report(label, res["worst"], _rounds_extra(res))
+    if given and case[7]:
+        dev = ref.check_rounds(lambda groups, R: _run(groups, max_iter=R, out="in place", device=True), g, label + " in place", ref.R_MAX)
+        assert dev["stop"] == res["stop"] and dev["J"] == res["J"]
+        _report(label + ", device chain in place", dev["worst"], _rounds_extra(dev))
+
+
+def test_groups_of_one_call_stop_in_different_rounds():
+    """six groups that stop in rounds of their own, or not at all: in one call, in reversed order and under round limits
+    at the smallest, a middle and the largest stop, every group's outputs and chain are those of its own call, bit for bit"""
+    rng = np.random.default_rng(830)
+    _, mixed, _ = ref.two_line_chain(rng)
+    th9, r9, _ = ref.planted(rng, 66, 9, 3, 1)
+    groups = [ref.rounds_case(ref.ROUNDS_CASES[0], True),                                          # crowded K = 3: stops
+              _group(mixed.reshape(-1, 7), 16, 2, 0, 1, mixed[0, 1, :6].reshape(2, 3)),            # the two-line chain
+              ref.rounds_case(ref.ROUNDS_CASES[4], False),                                         # crowded K = 17: does not stop
+              _group(np.full((9, 7), np.nan), 1, 2, 0, 1, np.array([[0.5, -5.0, 1.0], [1.0, 5.0, 2.0]])),      # every sample bad
+              _group(ref.crowded_chain(rng, 70, 1, 4, 2.5, 1)[0], 7, 1, 1, 1, np.array([[0.8, 0.0, 1.5, 1.2]]), pad=1),
+              _group(th9, 6, 9, 0, 1, r9, scale=np.ones(3), pad=2)]                                # planted K = 9, the truth as reference
+    base = _run(groups, max_iter=ref.R_MAX)
+    n_iter = [int(b["n_iter"]) for b in base]
+    print("relabel groups of one call: n_iter %s, n_changed %s" % (n_iter, [int(b["n_changed"]) for b in base]))
+    assert len(set(n_iter)) >= 3 and n_iter[2] == ref.R_MAX and base[2]["n_changed"] > 0 and n_iter[5] == 2 and n_iter[3] == n_iter[4] == 2
+    assert base[3]["n_used"] == 0 and base[0]["n_changed"] == 0 and 3 <= n_iter[0] < ref.R_MAX
+    stops = sorted({n for n, b in zip(n_iter, base) if b["n_changed"] == 0})
+    limits = sorted({stops[0], stops[len(stops) // 2], (stops[0] + stops[-1]) // 2, stops[-1], ref.R_MAX})
+    assert len(limits) >= 4
+    for R in limits:
+        both = base if R == ref.R_MAX else _run(groups, max_iter=R)
+        back = _run(groups[::-1], max_iter=R)[::-1]
+        for i, g in enumerate(groups):
+            alone = _run([g], max_iter=R)[0]
+            for got in (both[i], back[i]):
+                _same(alone, got)
+                assert np.array_equal(alone["out"], got["out"], equal_nan=True), (R, i)
+            assert alone["n_iter"] == min(R, n_iter[i]), (R, i)
+
+
+def test_the_product_s_chain_shape_180_by_64():
+    """n_keep = 180, W = 64 (11 520 samples), free sd, one- to four-line regions in one call of three rounds under the pooled
+    scale: k_colsum's 3 (q K = 3, 4) and 5 (q K = 6) workgroups per group and 15 at q K = 12.  The batched call's scale
+    and moments against numpy, every group alone against batched bit for bit, and the rounds checker at R_max = 3"""
+    rng = np.random.default_rng(840)
+    groups = []
+    for K, q in ((1, 3), (1, 4), (2, 3), (4, 3)):
+        th, start = ref.crowded_chain(rng, 11520, K, q, 2.5, 1)
+        groups.append(_group(th, 64, K, q - 3, 1, start))
+    got = _run(groups, max_iter=3)
+    for g, r in zip(groups, got):
+        K, q = g["K"], ref.Q_OF_MODE[g["mode"]]
+        label = "product shape 180 x 64, K=%d q=%d" % (K, q)
+        th = _samples(g)
+        v = ref.lines(th, K, q)[~ref.bad_samples(th, K, q)]
+        want = ref.pooled_scale(v)
+        assert r["n_bad"] == 2 and np.all(np.abs(r["scale"] - want) <= 1e-12 * np.maximum(1.0, np.abs(want))), label
+        worst = _check(r, g, label, max_iter=3)                     # counts, data movement, the moments under its own permutations
+        alone = _run([g], max_iter=3)[0]
+        _same(alone, r)
+        assert np.array_equal(alone["out"], r["out"], equal_nan=True), label
+        res = ref.check_rounds(lambda grp, R: _run(grp, max_iter=R), g, label, 3)
+        _report(label, max(worst, res["worst"]), _rounds_extra(res))
+
+
+def test_edges_of_the_first_stage_task_split():
+    """one | two workgroups of k_colsum (256 / (q K) chunks of 64 samples each): S = 5 440 | 5 441 at q K = 3, 4 096 | 4 097
+    at q K = 4, 2 688 | 2 689 at q K = 6, W = 1, under the pooled scale: scale and moments at the bars of every other case"""
+    rng = np.random.default_rng(850)
+    groups, labels = [], []
+    for K, q, S in ((1, 3, 5440), (1, 4, 4096), (2, 3, 2688)):
+        for extra in (0, 1):
+            th, start = ref.crowded_chain(rng, S + extra, K, q, 2.5, extra)
+            groups.append(_group(th, 1, K, q - 3, extra, start))
+            labels.append("first-stage split K=%d q=%d S=%d" % (K, q, S + extra))
+    for g, r, label in zip(groups, _run(groups), labels):
+        _report(label, _check(r, g, label))
+    for g, r, label in zip(groups, _run(groups, max_iter=2), labels):                              # the sums through the permutations
+        _check(r, g, label, max_iter=2)
+        assert r["n_iter"] == 2
 
 
 # ---- 5. end to end ----------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """CPU tests of the relabelling that undoes label switching: the numpy restatement (tests/relabel_ref.py) -- its two
 solvers against each other, a planted permutation, the planted error (a row-greedy assignment) against the optimality
-bar of the GPU comparison, the near-tie cap on the very inputs the GPU test uses --, the libvamp_relabel.so boundary
+bar of the GPU comparison, the near-tie cap on the very inputs the GPU test uses, the rounds checker on the restatement, the
+conditions on its case table and five planted errors of the host loop that must each fail it --, the libvamp_relabel.so boundary
 (build, exports, ctypes table, DESIGN's definitions, argument checks before any device call, the host header through a
 stand-alone program) and the Python wiring (mcmc.relabel, stats / trace / diagnostics with relabel=True, fits_relabel,
 Evidence.relabel, VPspectrum.relabel, do_vamp --relabel) with the library call replaced by the restatement."""
@@ -113,6 +114,78 @@ def test_near_ties_are_rare_on_the_inputs_of_the_exact_comparison(K, q):
     near = gap <= 2 * ref.bar(C_)
     print("K %d q %d: %d near ties of %d, smallest gap %.3g bars" % (K, q, near.sum(), len(gap), (gap / ref.bar(C_)).min()))
     assert near.mean() <= 0.01
+
+
+# ---- every round of the iteration: the rounds checker on the restatement, and on planted errors --------------------------
+_ROUNDS = {}
+
+
+def _restated_rounds(case, given):
+    """the rounds checker's result on the restatement, once per (case, scale)"""
+    if (case, given) not in _ROUNDS:
+        _ROUNDS[case, given] = ref.check_rounds(ref.restated_call(), ref.rounds_case(case, given), ref.rounds_label(case, given), ref.R_MAX)
+    return _ROUNDS[case, given]
+
+
+def test_crowded_chain_has_two_bad_samples_and_a_nan_in_an_sd_alone():
+    th, start = ref.crowded_chain(np.random.default_rng(303), 130, 9, 4, 2.5, sd=1)
+    assert th.shape == (130, 37) and start.shape == (9, 4) and np.array_equal(start, ref.lines(th, 9, 4)[0])
+    assert list(np.flatnonzero(ref.bad_samples(th, 9, 4))) == [43, 86] and np.isnan(th[43, 35]) and np.isinf(th[86, 1])
+    assert np.isnan(th[65, -1]) and np.isfinite(th[65, :-1]).all()
+    centres = np.sort(ref.lines(np.delete(th, [43, 86], axis=0), 9, 4)[:, :, 1], axis=1).mean(axis=0)
+    assert np.all(np.abs(np.diff(centres) - 2.5) < 0.5)                 # 2.5 jitters apart, shuffled in every sample
+    assert (ref.relabel(th, 9, 1, 1, start, None, 1)["n_switched"]) > 100
+
+
+@pytest.mark.parametrize("given", [True, False], ids=["given", "pooled"])
+@pytest.mark.parametrize("case", ref.ROUNDS_CASES, ids=lambda c: "K%d-q%d-sd%d-sep%g" % c[:4])
+def test_rounds_checker_passes_on_the_restatement(case, given):
+    """chained one-round calls against one R-round call for every R <= R_MAX, every round to the solver's bar, the
+    descent of J and the fixed point (relabel_ref.check_rounds), with the restatement in the library's place"""
+    res = _restated_rounds(case, given)
+    print("%s: stop %s, J %.6g -> %.6g in %d rounds, smallest gap %.3g bars" % (
+        ref.rounds_label(case, given), res["stop"], res["J"][0], res["J"][-1], len(res["J"]), res["gap"]))
+    assert res["stop"] is None or 2 <= res["stop"] <= ref.R_MAX
+    assert all(b <= a for a, b in zip(res["J"], res["J"][1:]))          # the restatement's J falls without any margin here
+
+
+def test_rounds_table_meets_the_conditions_the_gpu_comparison_relies_on():
+    """the table covers K = 3 (q = 3 and 4), 6, 9, 17, 32, sd 0 and 1, S = 192 (K <= 6) | 130 and W > 1 with padded rows
+    for every lane width; every lane width has a case that stops in 3 .. R_MAX rounds; a case does not stop within R_MAX;
+    no best / second-best gap of any round is below 1e3 bars where brute force applies (every cost matrix finite:
+    check_rounds asserts it)"""
+    from vamp_amd import relabel
+    assert ref.R_MAX <= 12 and relabel.DEFAULT_MAX_ITER <= ref.R_MAX
+    cases = ref.ROUNDS_CASES
+    assert {(c[0], c[1]) for c in cases} >= {(3, 3), (3, 4)} and {c[0] for c in cases} == {3, 6, 9, 17, 32} and {c[2] for c in cases} == {0, 1}
+    assert all(c[5] == (192 if c[0] <= 6 else 130) and c[5] % c[6] == 0 for c in cases)
+    width = lambda c: 8 if c[0] <= 8 else 16 if c[0] <= 16 else 32
+    assert {width(c) for c in cases if c[6] > 1 and c[7] > 0} == {8, 16, 32}
+    stops = {(c, gv): _restated_rounds(c, gv)["stop"] for c in cases for gv in (True, False)}
+    assert {width(c) for (c, gv), st in stops.items() if st is not None and 3 <= st <= ref.R_MAX} == {8, 16, 32}
+    assert any(st is None for (c, gv), st in stops.items() if c[0] in (17, 32))
+    assert len({st for st in stops.values()}) >= 4                     # and they do not all stop in the same round
+    for c in cases:
+        for gv in (True, False):
+            assert c[0] > ref.BRUTE_MAX_K or _restated_rounds(c, gv)["gap"] >= 1e3, c
+
+
+# the assertion of relabel_ref.check_rounds (or of check_round inside it) that each planted error of relabel_ref.relabel breaks
+_BREAKS = {
+    "means through the inverse permutation": r"round 1', 'label_mean'",        # check_round: the moments under its own permutations
+    "bad samples in the means' n": r"round 1', 'label_mean'",                  # the same assertion
+    "reference not moved": r"closure: perm of 2 rounds in one call is not that of chained round 2",
+    "prev never updated": r"closure: n_changed = \d+ after 2 rounds",
+    "n_iter is the round limit": r"closure: n_iter = 5 after 5 rounds in one call, chained stop 4",
+}
+
+
+@pytest.mark.parametrize("plant", ref.PLANTS)
+def test_rounds_checker_fails_on_a_planted_error(plant):
+    case = ref.ROUNDS_CASES[1]                                         # K = 3, q = 4, W = 6 with padded rows: stops in round 4
+    assert set(_BREAKS) == set(ref.PLANTS) and _restated_rounds(case, True)["stop"] == 4
+    with pytest.raises(AssertionError, match=_BREAKS[plant]):
+        ref.check_rounds(ref.restated_call(plant), ref.rounds_case(case, True), "planted", ref.R_MAX)
 
 
 # ---- the library boundary ----------------------------------------------------------------------------------------
