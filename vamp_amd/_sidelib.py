@@ -1,6 +1,6 @@
 """What the ctypes bindings of the side libraries (``_diag_lib``, ``_post_lib``, ``_evid_lib``, ``_pred_lib``,
-``_loo_lib``, ``_relabel_lib``, ``_fisher_lib``) and their callers (``diagnostics``, ``posterior``, ``evidence``,
-``predictive``, ``loo``, ``relabel``, ``fisher``) share; the second part is what the callers that walk every sample of a
+``_loo_lib``, ``_relabel_lib``, ``_fisher_lib``, ``_laplace_lib``) and their callers (``diagnostics``, ``posterior``,
+``evidence``, ``predictive``, ``loo``, ``relabel``, ``fisher``, ``laplace``) share; the second part is what the callers that walk every sample of a
 chain (``posterior``, ``predictive``, ``loo``, ``relabel``) hand their libraries alike; the third is what the two that
 evaluate the pointwise log-likelihood (``predictive``, ``loo``) do alike around their library call.
 

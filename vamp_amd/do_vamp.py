@@ -115,6 +115,12 @@ def fit_one(path, args, device=0):
         if args.output_folder is not None and getattr(spec, "output_filename", None):
             spec.write_fisher(fish)
         rec["fisher_seconds"] = time.perf_counter() - t1
+    if getattr(args, "laplace", False):
+        t1 = time.perf_counter()
+        lap = spec.laplace()
+        if args.output_folder is not None and getattr(spec, "output_filename", None):
+            spec.write_laplace(lap)
+        rec["laplace_seconds"] = time.perf_counter() - t1
     print("vamp_perf " + json.dumps(rec), flush=True)
     if args.output_folder is not None and getattr(spec, "output_filename", None):
         with open(spec.output_filename + "perf.json", "w") as fh:
@@ -184,6 +190,11 @@ def main(argv=None, _fit_name="vamp_amd.do_vamp:fit_one"):
                    help="also compute Fisher-matrix errors of every kept fit at the point it ended on (analytic Jacobian on the "
                         "GPU, no chain needed): 1-sigma errors per line, status and ln det per region, written to "
                         "<prefix>fisher.h5 (off by default; params.h5 is not changed)")
+    p.add_argument("--laplace", action="store_true",
+                   help="also estimate ln Z and the posterior's mean and standard deviations of every kept fit by importance "
+                        "sampling from the Gaussian N(MAP, Fisher covariance) on the GPU (no chain needed), with the Pareto "
+                        "khat that says whether the estimate may be trusted, written to <prefix>laplace.h5 (off by default; "
+                        "params.h5 is not changed)")
     p.add_argument("--relabel", action="store_true",
                    help="also undo label switching in the chains of the kept fits on the GPU: per region how many samples were "
                         "switched and the largest R-hat before and after, per line the mean and standard deviation of its "

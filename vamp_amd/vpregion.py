@@ -60,7 +60,11 @@ class VPregion():
         The first rung is judged by the LAST of its three BICs, as in the reference (:63).
         ``criterion='evidence'``: the number of lines is chosen by ln Z instead (``_region_fit_evidence``);
         ``criterion='waic'``: by the expected log predictive density of the chains (``_region_fit_waic``);
-        ``criterion='loo'``: the same ladder scored by PSIS-LOO (``_region_fit_loo``)."""
+        ``criterion='loo'``: the same ladder scored by PSIS-LOO (``_region_fit_loo``);
+        ``criterion='laplace'``: by ln Z from importance sampling at each rung's MAP (``_region_fit_laplace``;
+        ``evidence_kw``: keywords of ``VPfit.laplace``)."""
+        if criterion == 'laplace':
+            return self._region_fit_laplace(verbose, iterations, thin, burn, evidence_kw or {})
         if criterion == 'evidence':
             return self._region_fit_evidence(verbose, iterations, thin, burn, evidence_kw or {})
         if criterion == 'waic':
@@ -68,7 +72,7 @@ class VPregion():
         if criterion == 'loo':
             return self._region_fit_loo(verbose, iterations, thin, burn)
         if criterion != 'bic':
-            raise ValueError("criterion must be 'bic', 'evidence' or 'waic' or 'loo'")
+            raise ValueError("criterion must be 'bic', 'evidence' or 'waic' or 'loo' or 'laplace'")
         say = print if verbose else (lambda *a, **k: None)
         self._attempt += 1
         say("Setting initial number of lines to: {}".format(self.n))
@@ -188,6 +192,50 @@ class VPregion():
             kept = trial
         self.fit = kept
         self.fit.loo = self.loo[self.n]
+
+    def _region_fit_laplace(self, verbose, iterations, thin, burn, kw):
+        """Add a component while ln Z by Laplace importance sampling (vamp_amd.laplace) rises by more than the two rungs'
+        combined standard error.  Every rung is a ``_fit_n`` fit as on the BIC path, scored at the point it ended on
+        (``fit.laplace()``: no further chain).  A rung whose record cannot be trusted -- status not 0, or khat above
+        0.7 -- ends the ladder: it can neither be kept nor justify a further line, so the last trusted rung below it
+        stays (the first rung stays whatever it is), and ``self.laplace_stop`` = (rung, reason) says so (None when the
+        ladder ended on ln Z).  The records are kept as ``self.laplaces[n]``; the kept fit carries its record in its
+        ``laplace()`` cache."""
+        from . import laplace
+        say = print if verbose else (lambda *a, **k: None)
+        self._attempt += 1
+        self.laplace_stop = None
+
+        def distrust(n, rec):
+            if rec.status != 0:
+                return (n, "status {}".format(rec.status))
+            if not rec.khat <= laplace.HIGH_KHAT:
+                return (n, "khat {:.2f} above {}".format(rec.khat, laplace.HIGH_KHAT))
+            return None
+
+        say("Setting initial number of lines to: {}".format(self.n))
+        kept = self._fit_n(self.n, iterations, thin, burn)
+        self.laplaces = {self.n: kept.laplace(**kw)}
+        self.laplace_stop = distrust(self.n, self.laplaces[self.n])
+        while self.laplace_stop is None and self.n < min(MAX_COMPONENTS, laplace.MAX_COMPONENTS):
+            trial = self._fit_n(self.n + 1, iterations, thin, burn)
+            rec = self.laplaces[self.n + 1] = trial.laplace(**kw)
+            self.laplace_stop = distrust(self.n + 1, rec)
+            if self.laplace_stop is not None:
+                self._release(trial)
+                break
+            rise, se = rec.lnZ - self.laplaces[self.n].lnZ, float(np.hypot(self.laplaces[self.n].lnZ_se, rec.lnZ_se))
+            if not rise > se:
+                say("ln Z rose by {:.2f} (combined standard error {:.2f}): keeping n={}.".format(rise, se, self.n))
+                self._release(trial)
+                break
+            self.n += 1
+            say("ln Z rose by {:.2f} (combined standard error {:.2f}): n={}.".format(rise, se, self.n))
+            self._release(kept)
+            kept = trial
+        if self.laplace_stop is not None:
+            say("The {}-line rung is not to be trusted ({}): the ladder stops, keeping n={}.".format(*self.laplace_stop, self.n))
+        self.fit = kept
 
     @staticmethod
     def _release(fit):

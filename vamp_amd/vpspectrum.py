@@ -638,6 +638,47 @@ class VPspectrum():
         h5min.write(path, {k: np.array(v) for k, v in rec.items()})
         return path
 
+    def laplace(self, n_samples=4096, inflate=1.5, seed=None):
+        """After ``fit_spectrum`` (batched or not): Laplace importance sampling of every kept fit at the point it ended
+        on, from ONE Fisher call and ONE sampling call on the GPU (vamp_amd.laplace; each fit's ``laplace()`` cache is
+        filled).  It reads no chain.  A dict; per region [n_regions]: ``lnZ`` / ``lnZ_se`` / ``lnZ_psis`` /
+        ``lnZ_laplace`` / ``khat`` / ``ess``, ``n_out`` / ``status`` / ``n_comp`` (int32) and ``trusted`` (int8: status 0
+        and khat <= 0.7); per line, in ``fisher()``'s order and in the fit's units (amplitude; centre, frequency; sigma
+        or L_fwhm, G_fwhm, frequency): ``mean`` / ``sd`` [n_lines, q] (q = 4; the last column NaN for Gaussian lines)
+        with ``line_region`` [n_lines].  A fit of more lines than the library takes (16) is left out of the call and
+        has NaN rows and status -1."""
+        from . import laplace
+        fits = [r.fit for r in self.regions]
+        ok = [f._n <= laplace.MAX_COMPONENTS for f in fits]
+        got = iter(laplace.fits_laplace([f for f, o in zip(fits, ok) if o], n_samples=n_samples, inflate=inflate,
+                                        seed=laplace.DEFAULT_SEED if seed is None else seed, device=getattr(self, "device", 0)))
+        recs = [next(got) if o else None for o in ok]
+        col = lambda k: np.array([np.nan if r is None else getattr(r, k) for r in recs], dtype=np.float64)
+        out = {k: col(k) for k in ("lnZ", "lnZ_se", "lnZ_psis", "lnZ_laplace", "khat", "ess")}
+        out["n_out"] = np.array([0 if r is None else r.n_out for r in recs], dtype=np.int32)
+        out["status"] = np.array([-1 if r is None else r.status for r in recs], dtype=np.int32)
+        out["trusted"] = np.array([int(r is not None and r.ok) for r in recs], dtype=np.int8)
+        out["n_comp"] = np.array([f._n for f in fits], dtype=np.int32)
+        mean, sd, owner = [], [], []
+        for i, (f, r) in enumerate(zip(fits, recs)):
+            q = 4 if int(f._mode) == 1 else 3
+            for k in range(f._n):
+                m, s = np.full(4, np.nan), np.full(4, np.nan)
+                if r is not None:
+                    m[:q], s[:q] = r.mean[q * k:q * k + q], r.sd[q * k:q * k + q]
+                mean.append(m); sd.append(s); owner.append(i)
+        out["mean"] = np.array(mean, dtype=np.float64).reshape(len(owner), 4)
+        out["sd"] = np.array(sd, dtype=np.float64).reshape(len(owner), 4)
+        out["line_region"] = np.array(owner, dtype=np.int32)
+        return out
+
+    def write_laplace(self, rec):
+        """``laplace()``'s dict as ``<prefix>laplace.h5`` through vamp_amd/h5min.py; returns the path"""
+        from . import h5min
+        path = self.output_filename + 'laplace.h5'
+        h5min.write(path, {k: np.array(v) for k, v in rec.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
