@@ -12,7 +12,8 @@ Spectra are independent: no communication.  New flags: --walkers, --iterations, 
 ``<prefix>posterior.h5``: the posterior flux band and equivalent widths with credible intervals, vamp_amd.posterior),
 --evidence (also write ``<prefix>evidence.h5``: ln Z of every kept fit's model, vamp_amd.evidence), --predictive (also
 write ``<prefix>predictive.h5``: the pointwise log predictive density and WAIC of every kept fit, vamp_amd.predictive),
---loo (also write ``<prefix>loo.h5``: PSIS-LOO and the Pareto shape khat of every pixel of every kept fit, vamp_amd.loo).
+--loo (also write ``<prefix>loo.h5``: PSIS-LOO and the Pareto shape khat of every pixel of every kept fit, vamp_amd.loo),
+--hmc (also write ``<prefix>hmc.h5``: Hamiltonian Monte Carlo chains of every kept fit summarised, vamp_amd.hmc).
 """
 import argparse
 import glob
@@ -78,6 +79,7 @@ def perf_record(spec, path, seconds, batched):
 def fit_one(path, args, device=0):
     import json
     import time
+    import numpy as np
     from .vpspectrum import VPspectrum
     spec = VPspectrum(args.line, path, args.output_folder, voigt=args.voigt, chi_limit=1.5, mcmc_cov=False,
                       get_mcmc_err=True, convergence_attempts=args.conv_attempts, nwalkers=args.walkers,
@@ -125,6 +127,17 @@ def fit_one(path, args, device=0):
     if args.output_folder is not None and getattr(spec, "output_filename", None):
         with open(spec.output_filename + "perf.json", "w") as fh:
             json.dump(rec, fh)
+    if getattr(args, "hmc", False):
+        # After the perf record is out, which is what it is without the option: its own file and its own line
+        t1 = time.perf_counter()
+        chains = spec.hmc()
+        if args.output_folder is not None and getattr(spec, "output_filename", None):
+            spec.write_hmc(chains)
+        done = chains["status"] == 0
+        worst = chains["r_hat"][np.isfinite(chains["r_hat"])] if chains["r_hat"].size else chains["r_hat"]
+        print("vamp_hmc " + json.dumps({"spectrum": rec["spectrum"], "hmc_seconds": time.perf_counter() - t1, "regions_sampled": int(done.sum()),
+                                        "regions_without_chain": int((~done).sum()),
+                                        "max_r_hat": float(worst.max()) if worst.size else None}), flush=True)
     if getattr(args, "relabel", False):
         # After the perf record is out: it is what it is without the option, and a region without a chain must not cost
         # a finished fit its record.  Its own file and its own line; params.h5 and the harvest are not touched.
@@ -195,6 +208,11 @@ def main(argv=None, _fit_name="vamp_amd.do_vamp:fit_one"):
                         "sampling from the Gaussian N(MAP, Fisher covariance) on the GPU (no chain needed), with the Pareto "
                         "khat that says whether the estimate may be trusted, written to <prefix>laplace.h5 (off by default; "
                         "params.h5 is not changed)")
+    p.add_argument("--hmc", action="store_true",
+                   help="also sample every kept fit's posterior by Hamiltonian Monte Carlo on the GPU, preconditioned by the "
+                        "Fisher covariance and started at the point the fit ended on: per parameter the mean, standard deviation, "
+                        "quantiles, split-R-hat and n_eff, per region the acceptance rate and step size, written to <prefix>hmc.h5 "
+                        "(off by default; params.h5 and the perf record are not changed)")
     p.add_argument("--relabel", action="store_true",
                    help="also undo label switching in the chains of the kept fits on the GPU: per region how many samples were "
                         "switched and the largest R-hat before and after, per line the mean and standard deviation of its "

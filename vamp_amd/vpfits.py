@@ -442,6 +442,7 @@ class VPfit():
         self._lnp_chain = None
         self._fisher = None           # (point key, FisherRecord) of fisher(), for the point it was computed at
         self._laplace = None          # (point and argument key, LaplaceRecord) of laplace()
+        self._hmc = None              # (point and keyword key, HmcRecord) of hmc()
         self._set_values(self._theta_dev)
 
     # -- helpers ---------------------------------------------------------------------------
@@ -717,6 +718,17 @@ class VPfit():
 
     def _set_laplace(self, record, args):
         self._laplace = ((np.asarray(self._theta_dev, dtype=np.float64).tobytes(), tuple(args)), record)
+
+    def hmc(self, **kw):
+        """The fit's ``HmcRecord`` (vamp_amd.hmc) from its current point -- after ``map_estimate`` the MAP: chains of
+        Hamiltonian Monte Carlo in the metric of the Fisher covariance there, the step size tuned by a few short calls
+        first, in the caller's units and named like the traces; keywords as ``hmc.fits_hmc``.  It needs no stretch-move
+        chain and changes none.  Cached per fit until the point or a keyword changes."""
+        key = (np.asarray(self._theta_dev, dtype=np.float64).tobytes(), tuple(sorted(kw.items())))
+        if getattr(self, "_hmc", None) is None or self._hmc[0] != key:
+            from . import hmc
+            self._hmc = (key, hmc.fits_hmc([self], device=self.device, **kw)[0])
+        return self._hmc[1]
 
     def chain_covariance(self, n, voigt=False):
         """Per-component 3x3 covariance of (amplitude, sigma, centroid) samples (vpfits.py:432-456)."""

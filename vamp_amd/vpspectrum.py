@@ -679,6 +679,53 @@ class VPspectrum():
         h5min.write(path, {k: np.array(v) for k, v in rec.items()})
         return path
 
+    def hmc(self, **kw):
+        """After ``fit_spectrum`` (batched or not): Hamiltonian Monte Carlo chains of every kept fit from the point it ended
+        on (vamp_amd.hmc.fits_hmc, keywords as there: ONE Fisher call, a few tuning calls and ONE kept run for the whole
+        spectrum), and their convergence diagnostics from ONE call of libvamp_diag.so.  It reads no stretch-move chain and
+        changes none.  A dict; per region [n_regions]: ``status`` (0 ok, 1 no Fisher covariance: no chain, -1 more lines
+        than the library takes), ``accept_rate`` (mean over the chains), ``n_wall`` (steps that left the prior, all
+        chains), ``eps``, ``n_comp``, ``n_chains`` (those whose start was accepted); per parameter, the regions one after
+        the other and in the fit's units: ``mean`` / ``sd`` / ``r_hat`` / ``n_eff`` [n_par], ``quantiles`` [n_par, 3] (0.16,
+        0.5, 0.84) with ``par_region`` [n_par]."""
+        from . import diagnostics, hmc
+        fits = [r.fit for r in self.regions]
+        ok = [f._n <= hmc.MAX_COMPONENTS for f in fits]
+        got = iter(hmc.fits_hmc([f for f, o in zip(fits, ok) if o], device=getattr(self, "device", 0), **kw))
+        recs = [next(got) if o else None for o in ok]
+        have = [i for i, r in enumerate(recs) if r is not None and r.status == 0 and np.any(r.chain_status == 0)
+                and r.chain.shape[0] <= diagnostics.MAX_SAMPLES]
+        chains = [np.ascontiguousarray(recs[i].chain[:, recs[i].chain_status == 0, :]) for i in have]
+        diags = dict(zip(have, diagnostics.chain_diagnostics(chains, thin=[recs[i].thin for i in have], device=getattr(self, "device", 0)))) \
+            if have else {}
+        out = {"status": np.array([-1 if r is None else r.status for r in recs], dtype=np.int32),
+               "accept_rate": np.array([np.nan if r is None or r.status else np.nanmean(r.accept_rate) for r in recs], dtype=np.float64),
+               "n_wall": np.array([0 if r is None or r.status else int(np.sum(r.n_wall)) for r in recs], dtype=np.int32),
+               "eps": np.array([np.nan if r is None else r.eps for r in recs], dtype=np.float64),
+               "n_comp": np.array([f._n for f in fits], dtype=np.int32),
+               "n_chains": np.array([0 if r is None or r.status else int(np.sum(r.chain_status == 0)) for r in recs], dtype=np.int32)}
+        cols = {k: [] for k in ("mean", "sd", "r_hat", "n_eff")}
+        quant, owner = [], []
+        for i, (f, r) in enumerate(zip(fits, recs)):
+            D = len(f._scale)
+            mean, sd, q = (np.full(D, np.nan), np.full(D, np.nan), np.full((3, D), np.nan)) if r is None or r.status else r.summary()
+            d = diags.get(i)
+            cols["mean"].append(mean); cols["sd"].append(sd)
+            cols["r_hat"].append(np.full(D, np.nan) if d is None else d.r_hat)
+            cols["n_eff"].append(np.full(D, np.nan) if d is None else d.n_eff)
+            quant.append(q.T); owner += [i] * D
+        out.update({k: np.concatenate(v) if v else np.zeros(0) for k, v in cols.items()})
+        out["quantiles"] = np.concatenate(quant) if quant else np.zeros((0, 3))
+        out["par_region"] = np.array(owner, dtype=np.int32)
+        return out
+
+    def write_hmc(self, rec):
+        """``hmc()``'s dict as ``<prefix>hmc.h5`` through vamp_amd/h5min.py; returns the path"""
+        from . import h5min
+        path = self.output_filename + 'hmc.h5'
+        h5min.write(path, {k: np.array(v) for k, v in rec.items()})
+        return path
+
     def plot_spectrum(self):
         """total fit / components / residuals figures (vpspectrum.py:444-526); skipped without matplotlib"""
         try:
