@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-s
 # chain checks and the pass planner (chain_groups.hpp), the predictive density and PSIS-LOO the pointwise
 # log-likelihood stage (pointwise_ll.hpp): an edit of a shared header rebuilds what includes it
 SIDE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden"]
-POST_FLAGS = EVID_FLAGS = PRED_FLAGS = LOO_FLAGS = RELABEL_FLAGS = FISHER_FLAGS = LAPLACE_FLAGS = HMC_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
+POST_FLAGS = EVID_FLAGS = PRED_FLAGS = LOO_FLAGS = RELABEL_FLAGS = FISHER_FLAGS = LAPLACE_FLAGS = HMC_FLAGS = METRIC_FLAGS = SIDE_FLAGS      # (names the tests of those libraries read)
 SIDE_CALL = os.path.join(HERE, "csrc", "side_call.hpp")
 LANE_GROUP = os.path.join(HERE, "csrc", "lane_group.hpp")
 CHAIN_GROUPS = os.path.join(HERE, "csrc", "chain_groups.hpp")
@@ -92,6 +92,14 @@ HMC_OUT = os.path.join(HERE, "libvamp_hmc.so")
 HMC_DEPS = [HMC_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "csrc", "voigt_grad.hpp"),
             os.path.join(HERE, "csrc", "draws.hpp"), os.path.join(HERE, "..", "include", "vamp_hmc.h")]
 
+# libvamp_metric.so (include/vamp_metric.h): a positive-definite metric from any symmetric matrix, an eleventh library on
+# the same terms; it never sees parameters or data, so it shares the call frame and lane_group.hpp's lds_fence() only;
+# its host-side checks and launch plan are a plain C++ header (tests/host/metric_host.cpp)
+METRIC_SRC = os.path.join(HERE, "csrc", "metric.hip")
+METRIC_OUT = os.path.join(HERE, "libvamp_metric.so")
+METRIC_DEPS = [METRIC_SRC, SIDE_CALL, LANE_GROUP, os.path.join(HERE, "csrc", "voigt_math.hpp"), os.path.join(HERE, "csrc", "metric_host.hpp"),
+               os.path.join(HERE, "..", "include", "vamp_metric.h")]
+
 
 def _compile(out, src, deps, flags, force, verbose):
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
@@ -154,8 +162,13 @@ def build_hmc(force=False, verbose=True, out=None, defines=()):
     return _compile(out or HMC_OUT, HMC_SRC, HMC_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
+def build_metric(force=False, verbose=True, out=None, defines=()):
+    """libvamp_metric.so; returns its path.  ``out`` / ``defines``: a variant build beside it"""
+    return _compile(out or METRIC_OUT, METRIC_SRC, METRIC_DEPS, SIDE_FLAGS + ["-D" + d for d in defines], force, verbose)
+
+
 def build(force=False, verbose=True):
-    """The ten libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
+    """The eleven libraries; returns the path of libvamp_hip.so (tests/test_abi.py binds what this returns)."""
     build_diag(force=force, verbose=verbose)
     build_post(force=force, verbose=verbose)
     build_evid(force=force, verbose=verbose)
@@ -165,6 +178,7 @@ def build(force=False, verbose=True):
     build_fisher(force=force, verbose=verbose)
     build_laplace(force=force, verbose=verbose)
     build_hmc(force=force, verbose=verbose)
+    build_metric(force=force, verbose=verbose)
     return _compile(OUT, SRC, DEPS, FLAGS, force, verbose)
 
 

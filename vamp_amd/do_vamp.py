@@ -130,7 +130,7 @@ def fit_one(path, args, device=0):
     if getattr(args, "hmc", False):
         # After the perf record is out, which is what it is without the option: its own file and its own line
         t1 = time.perf_counter()
-        chains = spec.hmc()
+        chains = spec.hmc() if getattr(args, "metric", "fisher") == "fisher" else spec.hmc(metric=args.metric)
         if args.output_folder is not None and getattr(spec, "output_filename", None):
             spec.write_hmc(chains)
         done = chains["status"] == 0
@@ -213,6 +213,11 @@ def main(argv=None, _fit_name="vamp_amd.do_vamp:fit_one"):
                         "Fisher covariance and started at the point the fit ended on: per parameter the mean, standard deviation, "
                         "quantiles, split-R-hat and n_eff, per region the acceptance rate and step size, written to <prefix>hmc.h5 "
                         "(off by default; params.h5 and the perf record are not changed)")
+    p.add_argument("--metric", choices=("fisher", "regularised", "chain"), default="fisher",
+                   help="with --hmc: the metric of the chains.  fisher (the default) is the Fisher covariance; regularised takes "
+                        "the information in units of the priors' widths and raises its eigenvalues below 1 to 1 on the GPU, so a "
+                        "region whose information is singular or indefinite is sampled too; chain does the same with the covariance "
+                        "of the stretch-move chain.  <prefix>hmc.h5 then also holds n_low and n_high per region")
     p.add_argument("--relabel", action="store_true",
                    help="also undo label switching in the chains of the kept fits on the GPU: per region how many samples were "
                         "switched and the largest R-hat before and after, per line the mean and standard deviation of its "

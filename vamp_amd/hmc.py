@@ -24,6 +24,7 @@ from ._sidelib import Q_OF_MODE, per_group
 MAX_COMPONENTS, MAX_LEAP, MAX_CHAIN_ID = 16, 64, 1 << 26      # of include/vamp_hmc.h
 DEFAULT_SEED = 20110101
 QUANTILES = (0.16, 0.5, 0.84)
+METRICS = ("fisher", "regularised", "chain")
 
 _PER_CHAIN_I, _PER_CHAIN_D = ("n_accept", "n_wall", "chain_status"), ("dH_mean", "dH_max")
 _TRACE_MAT, _TRACE_VEC = ("mom", "prop", "prop_mom"), ("dH",)
@@ -41,12 +42,13 @@ class HmcRecord:
     ``n_wall`` (steps that left the prior), ``dH_mean`` / ``dH_max`` (of |dH| over the steps that met no wall) and
     ``chain_status`` (0 ok; 2 the start was rejected: that chain is NaN), ``status`` (0 ok; 1 no factor or no Fisher
     covariance: no chain), ``eps`` (the step size of the kept run), ``last`` [C, D] (the final state), ``n_steps``,
-    ``n_leap``, ``thin``, ``names`` (the fit's parameter names when the record was made from a fit, else None) and -- when
-    asked for, else None -- the per-step traces ``mom`` / ``prop`` / ``prop_mom`` [n_steps, C, D], ``dH`` and ``acc``
+    ``n_leap``, ``thin``, ``names`` (the fit's parameter names when the record was made from a fit, else None), ``metric``
+    (what ``fits_hmc`` took the factor from, else None) with ``n_low`` / ``n_high`` (the directions a regularised metric
+    repaired; None with the Fisher metric) and -- when asked for, else None -- the per-step traces ``mom`` / ``prop`` / ``prop_mom`` [n_steps, C, D], ``dH`` and ``acc``
     [n_steps, C]."""
 
     __slots__ = ("chain", "lnp", "accept_rate", "n_wall", "dH_mean", "dH_max", "chain_status", "status", "eps", "last", "n_steps",
-                 "n_leap", "thin", "names", "_diag") + TRACES
+                 "n_leap", "thin", "names", "_diag", "metric", "n_low", "n_high") + TRACES
 
     def __init__(self, **fields):
         for k in self.__slots__:
@@ -275,7 +277,7 @@ def tuned_eps(eps, accept, target_accept, factor=1.5):
 
 
 def fits_hmc(fits, n_chains=16, n_steps=400, n_burn=100, thin=1, n_leap=8, target_accept=0.8, tune_rounds=6, tune_steps=40, jitter=0.2,
-             seed=DEFAULT_SEED, device=0, want=()):
+             seed=DEFAULT_SEED, device=0, want=(), metric="fisher"):
     """Records of many ``VPfit`` objects from their current point (``fit._theta_dev``: the MAP after ``map_estimate``).  ONE
     ``fisher.fits_fisher`` call gives every region's covariance, whose Cholesky factor C is the metric; a region whose
     Fisher status is not 0 (or whose covariance does not factor) gets ``status`` 1 and no chain.  The chains start at MAP +
@@ -288,24 +290,41 @@ def fits_hmc(fits, n_chains=16, n_steps=400, n_burn=100, thin=1, n_leap=8, targe
 
     The defaults -- n_steps = 400 with n_burn = 100, six tuning rounds of 40 moves, the starting eps = D^(-1/4) (the
     scaling of the optimal step of a D-dimensional standard normal) and the jitter 0.2 -- are choices that have not been
-    measured until tools/bench_hmc.py has run (profiles/hmc_bench.txt)."""
-    from . import fisher
+    measured until tools/bench_hmc.py has run (profiles/hmc_bench.txt).
+
+    ``metric``: "fisher" is the above.  "regularised" takes the factor from ``metric.fits_metric(source="fisher")`` instead --
+    the information in prior units with its eigenvalues below 1 raised to 1, so a region whose information is singular or
+    indefinite still gets a metric -- and "chain" from ``metric.fits_metric(source="chain")``, the covariance of the fit's
+    stretch-move chain treated alike.  ``status`` 1 then means a metric status other than 0, and the records carry
+    ``n_low`` and ``n_high``."""
     fits = list(fits)
+    if metric not in METRICS:
+        raise ValueError(f"metric {metric!r} is not one of {METRICS}")
     if not fits:
         return []
-    fish = fisher.fits_fisher(fits, device=device)
+    if metric == "fisher":
+        from . import fisher
+        fish, repaired = fisher.fits_fisher(fits, device=device), None
+    else:
+        from . import metric as metric_mod
+        repaired = metric_mod.fits_metric(fits, source="fisher" if metric == "regularised" else "chain", device=device)
+        fish = repaired
     rng = np.random.default_rng(int(seed))
     G = len(fits)
     chols, starts, usable = [], [], []
     for f, r in zip(fits, fish):
         D = len(f._scale)
-        cov = r.cov / np.outer(f._scale, f._scale)             # back to the device units the point is in
         chol = np.full((D, D), np.nan)
-        if r.status == 0 and np.isfinite(cov).all():
-            try:
-                chol = np.linalg.cholesky(cov)
-            except np.linalg.LinAlgError:
-                pass
+        if repaired is not None:
+            if r.status == 0:
+                chol = np.asarray(r.chol, dtype=np.float64)
+        else:
+            cov = r.cov / np.outer(f._scale, f._scale)             # back to the device units the point is in
+            if r.status == 0 and np.isfinite(cov).all():
+                try:
+                    chol = np.linalg.cholesky(cov)
+                except np.linalg.LinAlgError:
+                    pass
         ok = bool(np.isfinite(chol).all())
         mode = int(f._mode)
         centre = np.asarray(f._theta_dev, dtype=np.float64)
@@ -329,6 +348,9 @@ def fits_hmc(fits, n_chains=16, n_steps=400, n_burn=100, thin=1, n_leap=8, targe
     recs = hmc_points(*data, state, chols, ks, modes, eps, n_steps=n_steps, n_burn=n_burn, thin=thin, n_leap=n_leap, jitter=jitter, seed=seed,
                       device=device, want=want, step0=step0)
     out = []
-    for f, r in zip(fits, recs):
+    for i, (f, r) in enumerate(zip(fits, recs)):
+        r.metric = metric
+        if repaired is not None:
+            r.n_low, r.n_high = int(repaired[i].n_low), int(repaired[i].n_high)
         out.append(r.to_units(f._scale, f._shift, names=f._names))
     return out

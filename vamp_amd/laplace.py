@@ -22,6 +22,7 @@ from ._sidelib import Q_OF_MODE, per_group
 
 MAX_COMPONENTS, MAX_SAMPLES = 16, 16384       # of include/vamp_laplace.h
 DEFAULT_SEED = 20110101
+METRICS = ("fisher", "regularised", "chain")
 HIGH_KHAT = 0.7                               # Vehtari et al.: above it the estimates are not to be trusted
 
 _GRP = ("lnZ", "lnZ_se", "lnZ_psis", "khat", "ess", "lnp_centre")
@@ -39,9 +40,10 @@ class LaplaceRecord:
     information), ``khat``, ``ess``, ``n_out`` (draws outside the prior or without a finite ln L), ``status`` (0 ok; 1 no
     proposal; 2 the centre is rejected by the target: everything NaN), ``mean`` / ``sd`` [D], ``cov`` [D, D],
     ``lnp_centre``, ``n_samples``, ``inflate``, ``names`` (the fit's parameter names when the record was made from a fit,
-    else None) and -- when asked for, else None -- the draws ``theta`` / ``z`` [S, D] and ``lnp`` / ``lnq`` / ``lw`` [S]."""
+    else None), ``metric`` (what ``fits_laplace`` took the proposal from, else None) with ``n_low`` / ``n_high`` (the
+    directions a regularised metric repaired; None with the Fisher metric) and -- when asked for, else None -- the draws ``theta`` / ``z`` [S, D] and ``lnp`` / ``lnq`` / ``lw`` [S]."""
 
-    __slots__ = _GRP + _CNT + _VEC + ("cov", "lnZ_laplace", "n_samples", "inflate", "names") + _SAMPLES
+    __slots__ = _GRP + _CNT + _VEC + ("cov", "lnZ_laplace", "n_samples", "inflate", "names", "metric", "n_low", "n_high") + _SAMPLES
 
     def __init__(self, **fields):
         for k in self.__slots__:
@@ -196,25 +198,41 @@ def laplace_points(xs, fluxes, noises, centres, covs, n_comp, mode, n_samples=40
     return recs[0] if single else recs
 
 
-def fits_laplace(fits, n_samples=4096, inflate=1.5, seed=DEFAULT_SEED, device=0, want=()):
+def fits_laplace(fits, n_samples=4096, inflate=1.5, seed=DEFAULT_SEED, device=0, want=(), metric="fisher"):
     """Records of many ``VPfit`` objects at their current point (``fit._theta_dev``: the MAP after ``map_estimate``): ONE
     ``fisher.fits_fisher`` call for the proposals' covariances, then ONE library call.  The bounds are those the library
     derives from the abscissa, as for ``evidence.log_evidence``; the draws are keyed by the fits' positions.  The records
     are in the caller's units (the affine map of ``VPfit._to_caller``) and named with the fits' parameter names; each fit's
-    ``laplace()`` cache is filled.  Returns the records, one per fit."""
-    from . import fisher
+    ``laplace()`` cache is filled.  Returns the records, one per fit.
+
+    ``metric``: "fisher" is the above.  "regularised" and "chain" take the proposal's covariance from
+    ``metric.fits_metric`` (source "fisher" / "chain") instead, so a region whose information is singular or indefinite
+    still gets a proposal; ``status`` 1 then means a metric status other than 0, ``lnZ_laplace`` uses the regularised
+    information, and the records carry ``n_low`` and ``n_high``."""
     fits = list(fits)
+    if metric not in METRICS:
+        raise ValueError(f"metric {metric!r} is not one of {METRICS}")
     if not fits:
         return []
-    fish = fisher.fits_fisher(fits, device=device)
-    # the Fisher records are in the caller's units: back to the device units the centre is in
-    covs = [r.cov / np.outer(f._scale, f._scale) for f, r in zip(fits, fish)]
+    repaired = None
+    if metric == "fisher":
+        from . import fisher
+        fish = fisher.fits_fisher(fits, device=device)
+        # the Fisher records are in the caller's units: back to the device units the centre is in
+        covs = [r.cov / np.outer(f._scale, f._scale) for f, r in zip(fits, fish)]
+    else:
+        from . import metric as metric_mod
+        fish = repaired = metric_mod.fits_metric(fits, source="fisher" if metric == "regularised" else "chain", device=device)
+        covs = [np.asarray(r.cov, dtype=np.float64) for r in repaired]
     recs = laplace_points([f._x for f in fits], [f._flux for f in fits], [None if f._sample_sd else f.noise for f in fits],
                           [np.asarray(f._theta_dev, dtype=np.float64) for f in fits], covs, [f._n for f in fits], [int(f._mode) for f in fits],
                           n_samples=n_samples, inflate=inflate, seed=seed, device=device, want=want, statuses=[r.status for r in fish])
     out = []
-    for f, r in zip(fits, recs):
+    for i, (f, r) in enumerate(zip(fits, recs)):
+        r.metric = metric
+        if repaired is not None:
+            r.n_low, r.n_high = int(repaired[i].n_low), int(repaired[i].n_high)
         rec = r.to_units(f._scale, f._shift, names=f._names)
-        f._set_laplace(rec, (int(n_samples), float(inflate), int(seed)))
+        f._set_laplace(rec, (int(n_samples), float(inflate), int(seed)) + (() if metric == "fisher" else (metric,)))
         out.append(rec)
     return out

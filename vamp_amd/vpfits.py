@@ -701,17 +701,19 @@ class VPfit():
     def _set_fisher(self, record, with_prior=True):
         self._fisher = ((np.asarray(self._theta_dev, dtype=np.float64).tobytes(), bool(with_prior)), record)
 
-    def laplace(self, n_samples=4096, inflate=1.5, seed=None):
+    def laplace(self, n_samples=4096, inflate=1.5, seed=None, metric="fisher"):
         """The fit's ``LaplaceRecord`` (vamp_amd.laplace) at its current point -- after ``map_estimate`` the MAP: ln Z with
         its standard error and the posterior's mean, standard deviations and covariance by importance sampling from
         N(point, inflate^2 Fisher covariance), in the caller's units and named like the traces, with the Pareto ``khat``
         that says whether they may be trusted (<= 0.7).  It needs no chain.  Two GPU calls (the Fisher matrix, the
-        draws), cached per fit until the point or an argument changes."""
+        draws), cached per fit until the point or an argument changes.  ``metric``: "fisher", or "regularised" / "chain" for
+        a proposal from ``vamp_amd.metric`` where the Fisher information is not positive definite."""
         from . import laplace
-        args = (int(n_samples), float(inflate), int(laplace.DEFAULT_SEED if seed is None else seed))
+        args = (int(n_samples), float(inflate), int(laplace.DEFAULT_SEED if seed is None else seed)) + (() if metric == "fisher" else (metric,))
         key = (np.asarray(self._theta_dev, dtype=np.float64).tobytes(), args)
         if getattr(self, "_laplace", None) is None or self._laplace[0] != key:
-            recs = laplace.fits_laplace([self], n_samples=args[0], inflate=args[1], seed=args[2], device=self.device)
+            kw = {} if metric == "fisher" else {"metric": metric}
+            recs = laplace.fits_laplace([self], n_samples=args[0], inflate=args[1], seed=args[2], device=self.device, **kw)
             if getattr(self, "_laplace", None) is None or self._laplace[0] != key:      # (fits_laplace fills the cache)
                 self._set_laplace(recs[0], args)
         return self._laplace[1]

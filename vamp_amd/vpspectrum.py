@@ -687,7 +687,8 @@ class VPspectrum():
         than the library takes), ``accept_rate`` (mean over the chains), ``n_wall`` (steps that left the prior, all
         chains), ``eps``, ``n_comp``, ``n_chains`` (those whose start was accepted); per parameter, the regions one after
         the other and in the fit's units: ``mean`` / ``sd`` / ``r_hat`` / ``n_eff`` [n_par], ``quantiles`` [n_par, 3] (0.16,
-        0.5, 0.84) with ``par_region`` [n_par]."""
+        0.5, 0.84) with ``par_region`` [n_par].  With ``metric`` = "regularised" or "chain" (vamp_amd.metric) also ``n_low`` /
+        ``n_high`` [n_regions], and ``status`` 1 means that the metric's status is not 0."""
         from . import diagnostics, hmc
         fits = [r.fit for r in self.regions]
         ok = [f._n <= hmc.MAX_COMPONENTS for f in fits]
@@ -704,6 +705,9 @@ class VPspectrum():
                "eps": np.array([np.nan if r is None else r.eps for r in recs], dtype=np.float64),
                "n_comp": np.array([f._n for f in fits], dtype=np.int32),
                "n_chains": np.array([0 if r is None or r.status else int(np.sum(r.chain_status == 0)) for r in recs], dtype=np.int32)}
+        if kw.get("metric", "fisher") != "fisher":      # the directions the regularised metric repaired (-1: no record)
+            out.update({k: np.array([-1 if r is None or getattr(r, k) is None else getattr(r, k) for r in recs], dtype=np.int32)
+                        for k in ("n_low", "n_high")})
         cols = {k: [] for k in ("mean", "sd", "r_hat", "n_eff")}
         quant, owner = [], []
         for i, (f, r) in enumerate(zip(fits, recs)):
