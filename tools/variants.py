@@ -16,9 +16,9 @@ Switches of the far-field tile loop that have a build of their own (see the #ifn
                                  records of a pair read by every lane one pair ahead)
   adj0=-DVAMP_DEAL_ADJ=0         a full batch is tiles p, p + 4, p + 8, p + 12 of a wavefront's class (default 1: four adjacent tiles, class p
                                  takes tiles 16 m + 4 p .. 16 m + 4 p + 3); switches the distant pass off with it
-  sup1=-DVAMP_SUPER_NODES=1      the lines distant from all four adjacent tiles of a batch once at the 16 nodes of the batch's super-tile,
-                                 eight per iteration, and interpolated (default 0: measured, faster on the headline, slower on the prior
-                                 ensemble, scratch reloads inside the loops; profiles/super_nodes_ab.txt)
+  sup0=-DVAMP_SUPER_NODES=0      every far line at the tiles' own nodes (default 1: the lines distant from all four adjacent tiles of a
+                                 batch once at the 16 nodes of the batch's super-tile, eight per iteration, and interpolated;
+                                 profiles/super_nodes_on_ab.txt)
   tab2=-DVAMP_TAB_PAIR=1         in-zone near lines: the Taylor table for two pixels of a lane at a time (default 0: measured, slower)
   head1=-DVAMP_TILE_HEAD=1       a tile's abscissae requested after the test that it is done from its moments (default 0: measured,
                                  inside the runs' spread)

@@ -125,11 +125,10 @@
 #define VAMP_DEAL_ADJ 1        // node pass: a full batch is four ADJACENT tiles, class p of PARTS takes tiles 16 m + 4 p .. 16 m + 4 p + 3 of
 #endif                         // every whole group of 16 tiles; 0: tiles p, p + 4, p + 8, p + 12.  What no group holds is dealt p, p + 4, ..
 #ifndef VAMP_SUPER_NODES
-#define VAMP_SUPER_NODES 0     // node pass (needs VAMP_DEAL_ADJ): the lines distant from all four tiles of a batch (vamp::ff_super_distant) once at
-#endif                         // the 16 nodes of the batch's super-tile, eight lines per iteration, and interpolated to the tiles' nodes (ff_super_pass).
-                               // Measured, off: -4.5 .. -5.7 % on the headline, but the prior ensemble, whose walkers never take the pass, runs 1.3 - 1.7 %
-                               // slower with it compiled in, chosen inside the one loop or as a copy of the loop of its own (SUPER), and with that copy
-                               // the headline kernel reloads spilled registers inside its loops (profiles/super_nodes_ab.txt)
+#define VAMP_SUPER_NODES 1     // node pass (needs VAMP_DEAL_ADJ): the lines distant from all four tiles of a batch (vamp::ff_super_distant) once at
+#endif                         // the 16 nodes of the batch's super-tile, eight lines per iteration, and interpolated to the tiles' nodes (ff_super_pass),
+                               // inside the one loop of the walkers without a guard bit, behind one scalar branch per batch that a walker with a line
+                               // wide for every tile does not take (profiles/super_nodes_on_ab.txt; the forms before it: profiles/super_nodes_ab.txt)
 #ifndef VAMP_TAB_PAIR
 #define VAMP_TAB_PAIR 0        // in-zone near lines: the Taylor table for two pixels of a lane at a time (table_eval2): measured, off
 #endif                         // (+0.4 % on the headline; profiles/tile_loop_waits_ab.txt); 0: one by one
@@ -1397,18 +1396,16 @@ __device__ __forceinline__ unsigned ff_fold16(unsigned long long m) {       // O
     const unsigned h = (unsigned)m | (unsigned)(m >> 32);
     return (h | (h >> 16)) & 0xffffu;
 }
-// the per-batch sets of lines, nested: n6 <= n4 <= n3 <= far (bit k: line k is far for some tile of the batch and the
-// deepest fraction any of those tiles needs has at least that many levels), and the lines wide for some tile
 #if VAMP_SUPER_NODES && VAMP_DEAL_ADJ
 #define VAMP_SUPER_ON 1
 #include "ff_super.inc"                // FF_SUPER_C (tools/gen_ff_super.py)
-// ... and (VAMP_SUPER_NODES) the lines distant from the batch's super-tile (Mid, Half), which are in none of the other
-// sets: dist, and d3 <= dist, those whose edge bound on the super-tile asks for three levels
-struct NodeSets { unsigned far, n6, n4, n3, wide, dist, d3; double Mid, Half; };
 #else
 #define VAMP_SUPER_ON 0
-struct NodeSets { unsigned far, n6, n4, n3, wide; };
 #endif
+// the per-batch sets of lines, nested: n6 <= n4 <= n3 <= far (bit k: line k is far for some tile of the batch and the
+// deepest fraction any of those tiles needs has at least that many levels), and the lines wide for some tile.  (The lines
+// distant from the batch's super-tile, VAMP_SUPER_NODES, are in none of them: ff_super_batch takes them out.)
+struct NodeSets { unsigned far, n6, n4, n3, wide; };
 // The classification of a FULL batch for the fp64 loop: ff_classify_batch's masks without its lists, plus the depth class
 // of every far pair from r2e = (dist s)^2 + y^2.  Every node of the tile lies inside it, at least `dist` from the line's
 // centre, so r2e is a lower bound of r2 at every node, and a deeper fraction is valid wherever a shallower one is.
@@ -1416,8 +1413,7 @@ struct NodeSets { unsigned far, n6, n4, n3, wide; };
 template <bool WIDE, bool ZONE, class LDS>
 __device__ __forceinline__ void ff_classify_batch_np(const LDS& L, const double2* __restrict__ geo, int K, int lane_, int base, int stride,
                                                      unsigned wide_all, unsigned long long& farmasks, unsigned long long& widemasks,
-                                                     unsigned long long& zonemasks, NodeSets& sets, double& mid, double& half,
-                                                     bool super_ok = false) {
+                                                     unsigned long long& zonemasks, NodeSets& sets, double& mid, double& half) {
     int lane = lane_;
     asm volatile("" : "+v"(lane));
     const int j = lane >> 4, k = lane & (KMAX - 1);
@@ -1443,24 +1439,6 @@ __device__ __forceinline__ void ff_classify_batch_np(const LDS& L, const double2
     sets.wide = ff_fold16(widemasks);
     zonemasks = 0ull;
     if constexpr (ZONE) zonemasks = __ballot(vamp::ff_tile_in_zone(my_c, my_s, my_y, mid, half));
-#if VAMP_SUPER_ON
-    // The batch's four ADJACENT tiles as one super-tile (super_ok: the caller's tiles are adjacent, the walker has neither a
-    // guard bit nor a line wide for every tile).  Line k has the same verdict on all four rows of lanes: one more ballot,
-    // and one for the depth.  A distant line stays in farmasks -- it is far, not near, for the tile loops -- and leaves the
-    // sets of the ordinary pairs; "far for every tile of the batch" is asked of the masks themselves, not of the rounding.
-    sets.dist = sets.d3 = 0u;
-    sets.Mid = sets.Half = 0.0;
-    if (super_ok) {
-        const double2 g0 = geo[base >> 8], g3 = geo[(base + (FF_BATCH - 1) * stride) >> 8];
-        vamp::ff_super_tile(g0.x, fabs(g0.y), g3.x, fabs(g3.y), sets.Mid, sets.Half);
-        const bool my_dist = (k < K) & vamp::ff_super_distant(my_c, my_s, my_y, sets.Mid, sets.Half);
-        const bool my_d3 = my_dist & (vamp::ff_super_r2e(my_c, my_s, my_y, sets.Mid, sets.Half) < VAMP_FF_R2_M2);
-        const unsigned all4 = (unsigned)farmasks & (unsigned)(farmasks >> 16) & (unsigned)(farmasks >> 32) & (unsigned)(farmasks >> 48) & 0xffffu;
-        sets.dist = (unsigned)__ballot(my_dist) & all4;
-        sets.d3 = (unsigned)__ballot(my_d3) & sets.dist;
-        sets.far &= ~sets.dist, sets.n6 &= ~sets.dist, sets.n4 &= ~sets.dist, sets.n3 &= ~sets.dist;
-    }
-#endif
 }
 // The node pass: lane 16 j + n ends with the node sum of (tile j, node n) -- far lines through the fractions, two lines per
 // iteration sharing a reciprocal (ff_frac2), deepest class first, M the class of the deeper of the two; then (WIDE) the
@@ -1472,7 +1450,8 @@ constexpr double FF_X_IDLE = 64.0;          // |z|^2 >= 4096: every fraction's r
 static_assert(FF_X_IDLE * FF_X_IDLE >= VAMP_FF_R2_M2 && FF_X_IDLE < vamp::X_FAR, "the idle argument neither deepens a pair nor needs a guard");
 template <int M> struct NpDepth { static constexpr int value = M; };       // the depth of a run of pairs (VAMP_NP_CLASS_RUNS)
 #if VAMP_SUPER_ON
-// The distant pass (VAMP_SUPER_NODES): the batch's distant lines (sets.dist, vamp::ff_super_distant) summed at the 16
+// The distant pass (VAMP_SUPER_NODES): the batch's distant lines (dist, and d3 <= dist, those whose edge bound on the
+// super-tile (Mid, Half) asks for three levels: ff_super_batch) summed at the 16
 // Chebyshev nodes of the batch's SUPER-tile and interpolated to the 64 (tile, node) points, which lane 16 j + n returns
 // for its own.  Lane 16 g + n evaluates at super-node n the lines of group g: slot 4 t + g of the eight lines of an
 // iteration (vamp::super_order), t = 0, 1 sharing a reciprocal as in ff_frac2; three levels while an iteration holds a
@@ -1482,10 +1461,10 @@ template <int M> struct NpDepth { static constexpr int value = M; };       // th
 // evaluates Clenshaw's recurrence at t = (xnode - Mid) / Half, the coefficients read at wave-uniform LDS addresses.
 template <class LDS>
 __device__ __forceinline__ double ff_super_pass(const LDS& L, TileScratch& Sx, const double* __restrict__ dct, int lane, double xnode,
-                                                const NodeSets& sets) {
-    const vamp::SuperOrder ord = vamp::super_order(sets.dist, sets.d3);
+                                                unsigned dist, unsigned d3, double Mid, double Half) {
+    const vamp::SuperOrder ord = vamp::super_order(dist, d3);
     const int n = lane & (FF_NODES - 1), g4 = (lane >> 4) * 4;
-    const double xs = fma(sets.Half, dct[FF_MAT + n], sets.Mid);
+    const double xs = fma(Half, dct[FF_MAT + n], Mid);
     unsigned long long seq = ord.seq;
     int left = ord.n;               // lines of the sequence not yet taken
     double acc = 0.0;
@@ -1538,7 +1517,7 @@ __device__ __forceinline__ double ff_super_pass(const LDS& L, TileScratch& Sx, c
     __builtin_amdgcn_wave_barrier();
     if (lane < FF_NODES) Sx.coef[lane] = a0 + a1;
     __builtin_amdgcn_wave_barrier();
-    const double t = (xnode - sets.Mid) * vamp::rcp_nr(sets.Half), t2 = t + t;
+    const double t = (xnode - Mid) * vamp::rcp_nr(Half), t2 = t + t;
     double b1 = 0.0, b2 = 0.0;
 #pragma unroll
     for (int k = FF_NODES - 1; k >= 1; --k) {
@@ -1550,22 +1529,45 @@ __device__ __forceinline__ double ff_super_pass(const LDS& L, TileScratch& Sx, c
     __builtin_amdgcn_wave_barrier();        // (the tile loops write Sx.coef next)
     return p;
 }
+// The distant lines of a full batch of four ADJACENT tiles, for a walker that may take the pass (no guard bit, no line wide
+// for every tile: the caller's one scalar branch per batch; everything of the pass is formed behind it).  The four tiles
+// as one super-tile: line k has the same verdict on all four rows of lanes, one ballot, and one for the depth; "far for
+// every tile of the batch" is asked of the masks themselves, not of the rounding.  A distant line stays in farmasks -- it
+// is far, not near, for the tile loops -- and leaves the sets of the ordinary pairs, from which alone ff_node_pass takes
+// its lines.  Returns the distant lines' sum at (tile lane >> 4, node lane & 15), the node pass's first addend.  The
+// lane's line and its tile's node are read again here and not carried over from the classification.
+template <class LDS>
+__device__ __forceinline__ double ff_super_batch(const LDS& L, TileScratch& Sx, const double* __restrict__ dct, const double2* __restrict__ geo,
+                                                 int K, int lane_, int base, int stride, double mid, double half,
+                                                 unsigned long long farmasks, NodeSets& sets) {
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    const int k = lane & (KMAX - 1);
+    const LineRec& me = *reinterpret_cast<const LineRec*>(reinterpret_cast<const char*>(L.line) +
+                                                          __umul24((unsigned)(k < K ? k : 0), (unsigned)sizeof(LineRec)));
+    const double my_c = me.c, my_s = me.s, my_y = me.y;
+    const double2 g0 = geo[base >> 8], g3 = geo[(base + (FF_BATCH - 1) * stride) >> 8];
+    double Mid, Half;
+    vamp::ff_super_tile(g0.x, fabs(g0.y), g3.x, fabs(g3.y), Mid, Half);
+    const bool my_dist = (k < K) & vamp::ff_super_distant(my_c, my_s, my_y, Mid, Half);
+    const bool my_d3 = my_dist & (vamp::ff_super_r2e(my_c, my_s, my_y, Mid, Half) < VAMP_FF_R2_M2);
+    const unsigned all4 = (unsigned)farmasks & (unsigned)(farmasks >> 16) & (unsigned)(farmasks >> 32) & (unsigned)(farmasks >> 48) & 0xffffu;
+    const unsigned dist = (unsigned)__ballot(my_dist) & all4;
+    if (dist == 0u) return 0.0;
+    const unsigned d3 = (unsigned)__ballot(my_d3) & dist;
+    sets.far &= ~dist, sets.n6 &= ~dist, sets.n4 &= ~dist, sets.n3 &= ~dist;
+    const double xnode = fma(half, dct[FF_MAT + (lane & (FF_NODES - 1))], mid);
+    return ff_super_pass(L, Sx, dct, lane, xnode, dist, d3, Mid, Half);
+}
 #endif
+// (fs0: what the lane's sum starts from -- ff_super_batch's share of it, or zero)
 template <bool WIDE, bool GUARD, class LDS>
 __device__ __forceinline__ double ff_node_pass(const LDS& L, const double* __restrict__ dct, const double* tab, int lane_, double mid, double half,
-                                               unsigned long long farmasks, unsigned long long widemasks, NodeSets sets,
-                                               TileScratch* Sx = nullptr) {
+                                               unsigned long long farmasks, unsigned long long widemasks, NodeSets sets, double fs0 = 0.0) {
     int lane = lane_;
     asm volatile("" : "+v"(lane));
     const double xnode = fma(half, dct[FF_MAT + (lane & (FF_NODES - 1))], mid);
-    double fs = 0.0;
-#if VAMP_SUPER_ON
-    // (a guard walker has no distant line: ff_classify_batch_np's super_ok)
-    if (sets.dist != 0u) {
-        fs = ff_super_pass(L, *Sx, dct, lane, xnode, sets);
-        farmasks &= ~(sets.dist * 0x0001000100010001ull);      // the ordinary pairs: the lines far for the tile and not distant
-    }
-#endif
+    double fs = fs0;
     const unsigned far16 = ff_tile_field(farmasks, lane);
 #if VAMP_NP_CLASS_RUNS
     // The pairs in vamp::np_pair_order's order, as one counted loop per depth: the constants of a depth are read once ahead
@@ -1693,6 +1695,11 @@ __device__ __forceinline__ double ff_node_pass(const LDS& L, const double* __res
 // ff_series for a value every lane holds for (tile lane >> 4, node lane & 15): row `j` hands over its tile's node values
 template <class real>
 __device__ __forceinline__ void ff_series_row(TileScratch& Sx, const double* __restrict__ dct, int lane, int j, double fs) {
+#if VAMP_SUPER_ON
+    // (the lane's node index is formed here: shared with the kernel's prologue it was spilled there, once the distant
+    //  pass stood in the batch loop, and reloaded from scratch in every tile)
+    asm volatile("" : "+v"(lane));
+#endif
     if ((lane >> 4) == j) Sx.coef[lane & (FF_NODES - 1)] = fs;
     __builtin_amdgcn_wave_barrier();
     const double2* mrow = reinterpret_cast<const double2*>(dct) + (lane < FF_ROWS ? lane : FF_ROWS - 1);
@@ -1764,12 +1771,20 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
     {
         NodeSets sets;
         double mid_j, half_j;
-#if VAMP_SUPER_ON
-        ff_classify_batch_np<WIDE, TAB>(L, geo, K, lane, batch, tstride, (unsigned)wide_all, farmasks, widemasks, zonemasks, sets, mid_j, half_j,
-                                        SUPER);
-        fsn = ff_node_pass<WIDE, GUARD>(L, dct, tab, lane, mid_j, half_j, farmasks, widemasks, sets, &Sx);
-#else
         ff_classify_batch_np<WIDE, TAB>(L, geo, K, lane, batch, tstride, (unsigned)wide_all, farmasks, widemasks, zonemasks, sets, mid_j, half_j);
+#if VAMP_SUPER_ON
+        // (SUPER: no guard bit.  Whether the walker takes the distant pass is a function of the walker alone -- no line wide for
+        //  every tile -- and wave-uniform, said as the loop's bounds are.  It is asked of the flags here, in every batch:
+        //  formed once ahead of the loop it is one scalar more across the loop, and the prior ensemble, whose walkers never
+        //  take the pass, ran 1.4 % slower; profiles/super_nodes_on_ab.txt)
+        double fs0 = 0.0;
+        if constexpr (SUPER) {
+            if (__builtin_amdgcn_readfirstlane((int)(unsigned)wide_all) == 0) {
+                fs0 = ff_super_batch(L, Sx, dct, geo, K, lane, batch, tstride, mid_j, half_j, farmasks, sets);
+            }
+        }
+        fsn = ff_node_pass<WIDE, GUARD>(L, dct, tab, lane, mid_j, half_j, farmasks, widemasks, sets, fs0);
+#else
         fsn = ff_node_pass<WIDE, GUARD>(L, dct, tab, lane, mid_j, half_j, farmasks, widemasks, sets);
 #endif
     }
@@ -1886,8 +1901,8 @@ __device__ __forceinline__ void sweep_range_ff_np(const RegionDev& R, const type
 #define VAMP_SUPER_ON 0
 #endif
 // the fp64 far-field sweep of a range as the library was built
-// (SUPER: the walker may take the distant pass -- no guard bit, no line wide for every tile; a copy of the loop of its own, as
-//  WIDE and GUARD have)
+// (SUPER: the loop of the walkers without a guard bit, which holds the distant pass; a walker with a line wide for every
+//  tile runs the same loop and skips the pass at one scalar branch per batch)
 template <int MODE, class PK, bool TAB, bool WIDE, bool GUARD, bool SUPER = false, class... Args>
 __device__ __forceinline__ void sweep_range_ff_any(Args&&... args) {
 #if VAMP_NODE_PASS_ON
@@ -2337,9 +2352,7 @@ __device__ __forceinline__ void sweep_class(const RegionDev& R, const typename P
                 const unsigned long long wide_all = (unsigned long long)(flags & 0xffff);
                 if (VAMP_MID_NODES || wide_all) {
                     if (guard) sweep_range_ff_any<MODE, PK, TAB, true, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
-                    else if (VAMP_SUPER_ON && wide_all == 0ull)
-                        sweep_range_ff_any<MODE, PK, TAB, true, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
-                    else sweep_range_ff_any<MODE, PK, TAB, true, false>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
+                    else sweep_range_ff_any<MODE, PK, TAB, true, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, wide_all, mom);
                 } else {
                     if (guard) sweep_range_ff_any<MODE, PK, TAB, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
                     else sweep_range_ff_any<MODE, PK, TAB, false, false, true>(R, L, Sx, dct, x, f, wt, ut, geo, lane, base0, full, stride, chi, tab, 0ull, mom);
@@ -2672,10 +2685,13 @@ __global__ __launch_bounds__(PackSplit::THREADS) void k_dbg_node_sums(const Regi
         unsigned long long farmasks, widemasks, zonemasks;
         NodeSets sets;
         double mid, half;
-        ff_classify_batch_np<true, true>(L, geo, K, lane, batch, tstride, wide_all, farmasks, widemasks, zonemasks, sets, mid, half,
-                                         adj && !guard && wide_all == 0u);
+        ff_classify_batch_np<true, true>(L, geo, K, lane, batch, tstride, wide_all, farmasks, widemasks, zonemasks, sets, mid, half);
+        double fs0 = 0.0;
+#if VAMP_SUPER_ON
+        if (adj && !guard && wide_all == 0u) fs0 = ff_super_batch(L, Sx, dct, geo, K, lane, batch, tstride, mid, half, farmasks, sets);
+#endif
         const double fs = guard ? ff_node_pass<true, true>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets)
-                                : ff_node_pass<true, false>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets, &Sx);
+                                : ff_node_pass<true, false>(L, dct, tab, lane, mid, half, farmasks, widemasks, sets, fs0);
         nodes[((batch + (lane >> 4) * tstride) >> 8) * FF_NODES + (lane & (FF_NODES - 1))] = fs;
         if (lane == 0) {
             unsigned* so = sets_out + (batch >> 8) * 5;
